@@ -9,6 +9,18 @@ seeded scene.  A "step" = `--views-per-step` (default 8) 
 operator forward + backward through the public GaussianRasterizer (the module render/uv_tex_render.py:40 builds),
 gradients accumulated into one flat fp32 bucket; with N>1 the bucket is all-reduced (RCCL, SUM) once per step --
 BASELINE configs[3]: 64-view batch over 8 GPUs = 8 views per rank per all-reduce.  value = views of all ranks / time.
+
+A plain run sets up, warms up, times the `--steps` steps and prints the line (value, ms_per_step, step percentiles).  Everything
+else it can measure -- the >= 2 s repeat of the step loop (value_long), the per-kernel table, the roofline figures, the same-run
+HBM copy ceiling, the reference call-pattern / iteration / retexture legs and the CPU baseline -- runs only with `--full` (and
+there the --no-* options below switch parts of it off).  The timed region is the same in both: the dominant kernel's HIP-event
+bracket inside it stays on; only --full reports what it measured.
+
+`--dump-outputs DIR` writes what the timed path computed in its LAST timed step, as a caller of that path receives it, to
+DIR/<name>.npy (float32): out_<color|depth|norm|alpha>[view, channel, pixel] and out_radii[view, gaussian] of the step's views in
+the order they ran, and grad_<leaf> (the flat gradient bucket's slice of each leaf, i.e. its .grad after the step; N > 1: after the
+all-reduce).  Larger arrays are a fixed seeded sample (_sample_index: the same positions in every run), < 64 MB in all.  The
+inputs (scene, cameras, upstream gradients) are seeded, so two builds run with the same arguments can be compared array by array.
 """
 import argparse
 import json
@@ -16,6 +28,7 @@ import math
 import os
 import sys
 import time
+import zlib
 
 import numpy as np
 import torch
@@ -50,6 +63,11 @@ def parse():
     ap.add_argument("--wire", default=os.environ.get("TEXGS_WIRE", "f32"), choices=["f32", "bf16-sh"],
                     help="N > 1: dtype of the gradient all-reduce on the wire.  bf16-sh = the view-dependent SH gradients (54 of the 150 MB "
                          "of a C3 bucket) are summed as bf16 -- GradBucket.all_reduce_async(wire_dtype=...) --, everything else stays f32")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline (kernel table, roofline, value_long, HBM ceiling, reference "
+                         "call-pattern / iteration / retexture legs, CPU baseline); a plain run times the steps and nothing else")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs and gradients of the last timed step to DIR/<name>.npy (see the module docstring; out/ is git-ignored)")
     ap.add_argument("--tex-res", type=int, default=0,
                     help="experiment: override the workload's cubemap resolution (e.g. C3 geometry with R = 2048: a 302 MB texture, past the "
                          "256 MB Infinity Cache); the metric string then says so and is never the headline")
@@ -68,7 +86,10 @@ def parse():
     ap.add_argument("--surface", default="textured", choices=["textured", "diff_gauss"],
                     help="diff_gauss = the untextured operator the reference's stages 1-2 call (render/render.py:75-84): same scene, "
                          "colours from SH with DC, no texture (SURVEY 8f-1); reported as its own metric, not the headline")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    return args
 
 
 def algorithmic_bytes(N, K, D, D_eff, P, T, R, n_vis, n_touched, texels_touched):
@@ -117,6 +138,48 @@ def cpu_baseline(scene, cam, W, H, with_bwd, budget_s=20.0):
             "sample": f"{views} whole view(s) fwd{'+bwd' if with_bwd else ''} of the same scene/camera by oracle/texgs_ref.c "
                       f"(gcc -O2 -fopenmp, fp32, {run.threads} OpenMP threads) in {el:.1f} s; D={run.D}",
             "seconds_measured": round(el, 2)}
+
+
+# ---- --dump-outputs: what the last timed step computed, for output-by-output comparison of two builds
+GRAD_SAMPLE = 1 << 20           # elements kept of a larger gradient
+PIXEL_BUDGET = 1 << 19          # sampled pixels over all views of the step (8 views: 65 536 each)
+RADII_BUDGET = 1 << 18          # sampled Gaussians' radii over all views of the step
+
+
+def _sample_index(name, n, k):
+    """Sorted positions of a fixed seeded sample of k of n (all of them when k >= n): the same in every run and every build."""
+    if k >= n:
+        return None
+    rng = np.random.default_rng(zlib.crc32(name.encode()))
+    return np.sort(rng.choice(n, size=k, replace=False))
+
+
+def _take(t, name, k):
+    """t [..., n] -> t[..., sample] as a float32 host array."""
+    t = t.detach()
+    idx = _sample_index(name, t.shape[-1], k)
+    if idx is not None:
+        t = t.index_select(t.dim() - 1, torch.from_numpy(idx).to(t.device))
+    return t.float().cpu().numpy()
+
+
+def dump_outputs(out_dir, step_outs, grads):
+    """step_outs: the forward outputs (color, depth, norm, alpha, radii, ...) of each view of the step, in the order they ran;
+    grads: {leaf name: gradient tensor}.  Writes out_dir/<name>.npy, returns the total bytes written."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {}
+    views = len(step_outs)
+    for i, kind in enumerate(("color", "depth", "norm", "alpha")):
+        st = torch.stack([o[i].detach() for o in step_outs])                   # [V, C, H, W]
+        arrays["out_" + kind] = _take(st.flatten(2), "pixels", max(1, PIXEL_BUDGET // views))
+    arrays["out_radii"] = _take(torch.stack([o[4] for o in step_outs]), "radii", max(1, RADII_BUDGET // views))
+    for name, g in grads.items():
+        arrays["grad_" + name] = _take(g.reshape(-1), "grad_" + name, GRAD_SAMPLE)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total < 64 << 20, total
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return total
 
 
 def main():
@@ -252,7 +315,8 @@ def main():
 
     step_recs = []          # N > 1: (start, render done, all-reduce waited for) events of the timed steps, this rank
 
-    def step(p=pipe, rec=None):
+    def step(p=pipe, rec=None, keep=False):
+        """keep: return the views' forward outputs (otherwise dropped with the step, as before)."""
         if rec is not None:
             ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
             ev[0].record()
@@ -263,7 +327,7 @@ def main():
         two = with_bwd and dist is not None and args.order == "accumulate" and seg_tex is not None
         # the texture half of the bucket is all-reduced on a side stream as soon as the last view's texture-gradient reduce has been
         # issued (it overlaps that view's K8 and the host's end-of-step work); the per-Gaussian half after the last K8
-        p.run(batch, view_fwd, view_bwd if with_bwd else None, sink=bucket, order=args.order,
+        outs = p.run(batch, view_fwd, view_bwd if with_bwd else None, sink=bucket, order=args.order,
               texture_ready=(lambda evs: bucket.all_reduce_async(dist, seg_tex, after=evs, timing=True)) if two else None,
               prefetch_fn=view_prefetch if (args.prefetch and p.streams and not untextured and with_bwd) else None,   # (forward-only: nothing to get ahead of)
               prefetch_ahead=int(os.environ.get("TEXGS_BENCH_PREFETCH_AHEAD", "1")))
@@ -282,6 +346,7 @@ def main():
         if rec is not None:
             ev[2].record()
             rec.append(ev)
+        return outs if keep else None
 
     def fence():
         torch.cuda.synchronize(dev)
@@ -300,62 +365,70 @@ def main():
         step()
     fence()
     # HIP events inside the timed region bracket ONLY the dominant kernel (an event pair costs ~5 us of stream time; all
-    # nine kernel groups bracketed cost ~90 us / view).  The full per-kernel table comes from two extra steps afterwards.
+    # nine kernel groups bracketed cost ~90 us / view).  The full per-kernel table comes from two extra steps afterwards (--full).
+    # The bracket stays on in a plain run too: the timed region, and with it `value`, is the same with or without --full.
     DOMINANT = "render_bwd" if with_bwd else "render_fwd"
     _lib.profile_enable(True, only=[DOMINANT])
     _lib.profile_read()
     step_ev = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
+    last_outs = None
     t0 = time.perf_counter()
     step_ev[0].record()
     for k in range(args.steps):
-        step(rec=step_recs if dist is not None else None)
+        last_outs = step(rec=step_recs if dist is not None else None, keep=bool(args.dump_outputs) and k == args.steps - 1)
         step_ev[k + 1].record()
     fence()
     t1 = time.perf_counter()
     kern_timed = _lib.profile_read()
     comm = bucket.comm_timings() if (with_bwd and dist is not None) else []
-    # the same step loop again for >= 2 s (the mandated K steps are a fraction of a second -- too short for an outside
-    # sampler to see the GPU busy); reported beside `value`, never instead of it
     _lib.profile_enable(False)
-    el_max = t1 - t0
-    if dist is not None:        # (every rank must run the SAME number of steps: they contain collectives)
-        te = torch.tensor([el_max], device=dev if backend == "nccl" else "cpu", dtype=torch.float64)
-        dist.all_reduce(te, op=dist.ReduceOp.MAX)
-        el_max = float(te.item())
-    long_steps = min(4096, max(args.steps, int(math.ceil(2.2 / max(el_max / args.steps, 1e-6)))))
-    fence()
-    tl0 = time.perf_counter()
-    for _ in range(long_steps):
-        step()
-    fence()
-    long_elapsed = time.perf_counter() - tl0
-    if dist is not None:
-        tl = torch.tensor([long_elapsed], device=dev if backend == "nccl" else "cpu", dtype=torch.float64)
-        dist.all_reduce(tl, op=dist.ReduceOp.MAX)
-        long_elapsed = float(tl.item())
-    value_long = long_steps * args.views_per_step * world / long_elapsed
-    if with_bwd and dist is not None:
-        bucket.comm_timings()           # (drop the long loop's entries: `comm` above is the timed region's)
-    # the per-kernel table: two extra steps with every kernel group bracketed, views one after the other on one stream, so
-    # that each duration is the kernel's own (in the pipelined region a kernel shares the GPU with other views' kernels)
-    kern = dict(kern_timed)
-    kern_solo_dom = (0.0, 0)
-    if not args.no_kernel_table:
+    if args.dump_outputs and rank == 0:       # before anything else runs a step: the bucket still holds the last timed step's sum
+        grads = {n: p_.grad for n, p_ in list(leaves.items()) + [("means2D", means2D)] if p_.grad is not None} if with_bwd else {}
+        dump_outputs(args.dump_outputs, last_outs, grads)
+    del last_outs
+    value_long = long_elapsed = long_steps = None
+    kern, kern_solo_dom = {}, (0.0, 0)
+    if args.full:
+        # the same step loop again for >= 2 s (the mandated K steps are a fraction of a second -- too short for an outside
+        # sampler to see the GPU busy); reported beside `value`, never instead of it
+        el_max = t1 - t0
+        if dist is not None:        # (every rank must run the SAME number of steps: they contain collectives)
+            te = torch.tensor([el_max], device=dev if backend == "nccl" else "cpu", dtype=torch.float64)
+            dist.all_reduce(te, op=dist.ReduceOp.MAX)
+            el_max = float(te.item())
+        long_steps = min(4096, max(args.steps, int(math.ceil(2.2 / max(el_max / args.steps, 1e-6)))))
+        fence()
+        tl0 = time.perf_counter()
+        for _ in range(long_steps):
+            step()
+        fence()
+        long_elapsed = time.perf_counter() - tl0
+        if dist is not None:
+            tl = torch.tensor([long_elapsed], device=dev if backend == "nccl" else "cpu", dtype=torch.float64)
+            dist.all_reduce(tl, op=dist.ReduceOp.MAX)
+            long_elapsed = float(tl.item())
+        value_long = long_steps * args.views_per_step * world / long_elapsed
+        if with_bwd and dist is not None:
+            bucket.comm_timings()           # (drop the long loop's entries: `comm` above is the timed region's)
+        # the per-kernel table: two extra steps with every kernel group bracketed, views one after the other on one stream, so
+        # that each duration is the kernel's own (in the pipelined region a kernel shares the GPU with other views' kernels)
+        kern = dict(kern_timed)
+        if not args.no_kernel_table:
+            _lib.profile_enable(False)
+            for _ in range(2):      # the serial path runs on another stream: its per-stream scratch (texture-bin capacity) adapts first
+                step(pipe_serial)
+            fence()
+            _lib.profile_enable(True, only=[DOMINANT])
+            step(pipe_serial)
+            fence()
+            kern_solo_dom = _lib.profile_read()[DOMINANT]      # the dominant kernel alone on the GPU, only it bracketed
+            _lib.profile_enable(True)
+            for _ in range(2):
+                step(pipe_serial)
+            fence()
+            kern = _lib.profile_read()
         _lib.profile_enable(False)
-        for _ in range(2):      # the serial path runs on another stream: its per-stream scratch (texture-bin capacity) adapts first
-            step(pipe_serial)
-        fence()
-        _lib.profile_enable(True, only=[DOMINANT])
-        step(pipe_serial)
-        fence()
-        kern_solo_dom = _lib.profile_read()[DOMINANT]      # the dominant kernel alone on the GPU, only it bracketed
-        _lib.profile_enable(True)
-        for _ in range(2):
-            step(pipe_serial)
-        fence()
-        kern = _lib.profile_read()
-    _lib.profile_enable(False)
-    kern[DOMINANT] = kern_timed[DOMINANT]
+        kern[DOMINANT] = kern_timed[DOMINANT]
     # N > 1: what every rank did in the timed region, gathered to rank 0 (the first real multi-GPU run must be
     # diagnosable from its one JSON line): its views and their instance counts, GPU time of the rendering part of a step, the part
     # of the all-reduce the compute stream had to wait for, the collectives' own durations on the comm stream (call order)
@@ -384,217 +457,221 @@ def main():
     total_views = args.steps * args.views_per_step * world
     value = total_views / elapsed
 
-    # ---- units of one representative launch (view my_views[0]), outside the timed region
-    st0 = settings(cams[my_views[0]])
-    with torch.no_grad():
-        if untextured:
-            outs, s = forward_raw(st0, leaves["means3D"].detach(), leaves["shs"].detach()[:, 1:, :].contiguous(), leaves["opacities"].detach(),
-                                  leaves["scales"].detach(), leaves["rotations"].detach(), None, None, None,
-                                  color_offset=(0.28209479177387814 * leaves["shs"].detach()[:, 0, :]).contiguous())
-        else:
-            outs, s = forward_raw(st0, leaves["means3D"].detach(), leaves["shs"].detach(), leaves["opacities"].detach(),
-                                  leaves["scales"].detach(), leaves["rotations"].detach(), leaves["uvs"].detach(), juv,
-                                  leaves["texture"].detach())
-        T = s.tensors["ranges"].shape[0]
-        nc = s.tensors["n_contrib"].to(torch.int64)
-        tx, ty = (W + 15) // 16, (H + 15) // 16
-        pad = torch.zeros(ty * 16, tx * 16, dtype=torch.int64, device=dev)
-        pad[:H, :W] = nc
-        D_eff = int(pad.reshape(ty, 16, tx, 16).amax(dim=(1, 3)).sum())
-        n_vis = int((outs[4] > 0).sum())
-        n_touched, texels = n_vis, 0
-        if with_bwd:
-            res = backward_raw(s, g_img, None, g_norm, g_alpha)
-            n_touched = int((res[3].reshape(N, -1).abs().sum(1) > 0).sum())     # Gaussians that received a gradient
-            texels = 0 if untextured else int((res[7].abs().sum(-1) > 0).sum())
-        else:
-            texels = 0
-    ab = algorithmic_bytes(N, K, s.D, D_eff, P, T, R, n_vis, n_touched, texels)
+    # ---- --full: everything beside the headline, after the timed region
+    s = D_eff = view_bytes = roofline = hbm_measured = compat = ref_iter = retex = cpu = None
     kinfo = {}
-    for name, (ms, cnt) in kern.items():
-        if cnt:
-            kinfo[name] = {"avg_us": 1e3 * ms / cnt, "launches": cnt, "alg_MB": ab.get(name, 0) / 1e6,
-                           "GBps": ab.get(name, 0) / (ms / cnt * 1e-3) / 1e9}
-    dom = max(kinfo, key=lambda k: kinfo[k]["avg_us"]) if kinfo else None        # every group launches once per view
-    roofline = None
-    traffic = None
-    traffic_all = None
-    traffic_source = None
-    # PMC pass of the same command (scripts/prof.sh + scripts/make_traffic.py), used only if it was measured on THESE kernel sources
-    tfiles = sorted(f for f in os.listdir(os.path.join(ROOT, "profiles")) if f.endswith("_traffic.json")) if os.path.isdir(os.path.join(ROOT, "profiles")) else []
-    if dom and args.workload == "c3" and not args.tex_res and not untextured and tfiles:
-        try:
-            sys.path.insert(0, os.path.join(ROOT, "scripts"))
-            from make_traffic import source_hash
-            tj = json.load(open(os.path.join(ROOT, "profiles", tfiles[-1])))
-            if tj.get("_kernel_source_hash") == source_hash():
-                traffic = tj.get(dom, {}).get("traffic_bytes")
-                traffic_all = {k: v for k, v in tj.items() if not k.startswith("_")}
-                traffic_source = (f"profiles/{tfiles[-1]} (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this workload with --streams 1 on "
-                                  f"these kernel sources, hash {tj['_kernel_source_hash']}; {tj.get('_calibration', '')})")
+    if args.full:
+        # ---- units of one representative launch (view my_views[0]), outside the timed region
+        st0 = settings(cams[my_views[0]])
+        with torch.no_grad():
+            if untextured:
+                outs, s = forward_raw(st0, leaves["means3D"].detach(), leaves["shs"].detach()[:, 1:, :].contiguous(), leaves["opacities"].detach(),
+                                      leaves["scales"].detach(), leaves["rotations"].detach(), None, None, None,
+                                      color_offset=(0.28209479177387814 * leaves["shs"].detach()[:, 0, :]).contiguous())
             else:
-                traffic_source = f"profiles/{tfiles[-1]} was measured on other kernel sources (hash mismatch): not used"
-        except Exception as e:          # noqa: BLE001
-            traffic_source = f"no usable traffic file ({type(e).__name__})"
-    if dom:
-        ach = kinfo[dom]["GBps"]
-        roofline = {"bound": "hbm", "kernel": dom, "achieved": round(ach, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": round(ach / HBM_PEAK_GBS, 5), "traffic": traffic, "traffic_source": traffic_source,
-                    "alg_bytes_per_launch": ab[dom], "avg_launch_us": round(kinfo[dom]["avg_us"], 2)}
-        # the same figure on SURVEY.md section 8(d)'s terms for the two blend kernels (K7: 52 P + 116 D + 228 N + 216 R^2, K6:
-        # 116 D + 72 R^2 + 40 P + 8 T -- whole lists and the whole texture, where this file's own definition counts the list up to
-        # the last contributor and the texels actually touched: the smaller, stricter number stays `achieved`)
-        sv = {"render_bwd": 52 * P + 116 * s.D + 228 * N + 216 * R * R, "render_fwd": 116 * s.D + 72 * R * R + 40 * P + 8 * T}.get(dom)
-        if sv and not untextured:
-            roofline["alg_bytes_per_launch_survey_8d"] = sv
-            roofline["frac_survey_8d"] = round(sv / (kinfo[dom]["avg_us"] * 1e-6) / 1e9 / HBM_PEAK_GBS, 5)
-        if traffic_all:
-            # every kernel group's measured past-L2 traffic per view beside its algorithmic bytes (VERDICT r5 #3 iii): the ratio is
-            # what the gather / scatter access patterns cost on top of the compulsory bytes
-            tb = {k: {"traffic_MB": round(v["traffic_bytes"] / 1e6, 1), "alg_MB": round(ab.get(k, 0) / 1e6, 1),
-                      "traffic_over_alg": (round(v["traffic_bytes"] / ab[k], 2) if ab.get(k) else None)} for k, v in traffic_all.items()}
-            ttot = sum(v["traffic_bytes"] for v in traffic_all.values())
-            roofline["traffic_by_kernel_per_view"] = tb
-            roofline["traffic_total_per_view_MB"] = round(ttot / 1e6, 1)
-            roofline["traffic_total_over_alg"] = round(ttot / max(sum(ab.values()), 1), 2)
-            roofline["traffic_rate_at_value_GBps"] = round(ttot * value / world / 1e9, 1)
-        if dom == DOMINANT and kern_solo_dom[1]:
-            solo_us = 1e3 * kern_solo_dom[0] / kern_solo_dom[1]
-            roofline["solo_launch_us"] = round(solo_us, 2)
-            roofline["solo_frac"] = round(ab[dom] / (solo_us * 1e-6) / 1e9 / HBM_PEAK_GBS, 5)
-            if args.streams > 1:
-                roofline["note"] = (f"achieved / frac use the launch duration inside the timed region, where {args.streams} views are in "
-                                    "flight on separate HIP streams and the kernel shares the GPU with other views' kernels; solo_* is "
-                                    "the same kernel with the views run one after the other (extra steps after the timed region)")
-    view_bytes = sum(ab[k] for k in ab if (with_bwd or k not in ("render_bwd", "preprocess_bwd")))
+                outs, s = forward_raw(st0, leaves["means3D"].detach(), leaves["shs"].detach(), leaves["opacities"].detach(),
+                                      leaves["scales"].detach(), leaves["rotations"].detach(), leaves["uvs"].detach(), juv,
+                                      leaves["texture"].detach())
+            T = s.tensors["ranges"].shape[0]
+            nc = s.tensors["n_contrib"].to(torch.int64)
+            tx, ty = (W + 15) // 16, (H + 15) // 16
+            pad = torch.zeros(ty * 16, tx * 16, dtype=torch.int64, device=dev)
+            pad[:H, :W] = nc
+            D_eff = int(pad.reshape(ty, 16, tx, 16).amax(dim=(1, 3)).sum())
+            n_vis = int((outs[4] > 0).sum())
+            n_touched, texels = n_vis, 0
+            if with_bwd:
+                res = backward_raw(s, g_img, None, g_norm, g_alpha)
+                n_touched = int((res[3].reshape(N, -1).abs().sum(1) > 0).sum())     # Gaussians that received a gradient
+                texels = 0 if untextured else int((res[7].abs().sum(-1) > 0).sum())
+            else:
+                texels = 0
+        ab = algorithmic_bytes(N, K, s.D, D_eff, P, T, R, n_vis, n_touched, texels)
+        kinfo = {}
+        for name, (ms, cnt) in kern.items():
+            if cnt:
+                kinfo[name] = {"avg_us": 1e3 * ms / cnt, "launches": cnt, "alg_MB": ab.get(name, 0) / 1e6,
+                               "GBps": ab.get(name, 0) / (ms / cnt * 1e-3) / 1e9}
+        dom = max(kinfo, key=lambda k: kinfo[k]["avg_us"]) if kinfo else None        # every group launches once per view
+        roofline = None
+        traffic = None
+        traffic_all = None
+        traffic_source = None
+        # PMC pass of the same command (scripts/prof.sh + scripts/make_traffic.py), used only if it was measured on THESE kernel sources
+        tfiles = sorted(f for f in os.listdir(os.path.join(ROOT, "profiles")) if f.endswith("_traffic.json")) if os.path.isdir(os.path.join(ROOT, "profiles")) else []
+        if dom and args.workload == "c3" and not args.tex_res and not untextured and tfiles:
+            try:
+                sys.path.insert(0, os.path.join(ROOT, "scripts"))
+                from make_traffic import source_hash
+                tj = json.load(open(os.path.join(ROOT, "profiles", tfiles[-1])))
+                if tj.get("_kernel_source_hash") == source_hash():
+                    traffic = tj.get(dom, {}).get("traffic_bytes")
+                    traffic_all = {k: v for k, v in tj.items() if not k.startswith("_")}
+                    traffic_source = (f"profiles/{tfiles[-1]} (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this workload with --streams 1 on "
+                                      f"these kernel sources, hash {tj['_kernel_source_hash']}; {tj.get('_calibration', '')})")
+                else:
+                    traffic_source = f"profiles/{tfiles[-1]} was measured on other kernel sources (hash mismatch): not used"
+            except Exception as e:          # noqa: BLE001
+                traffic_source = f"no usable traffic file ({type(e).__name__})"
+        if dom:
+            ach = kinfo[dom]["GBps"]
+            roofline = {"bound": "hbm", "kernel": dom, "achieved": round(ach, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": round(ach / HBM_PEAK_GBS, 5), "traffic": traffic, "traffic_source": traffic_source,
+                        "alg_bytes_per_launch": ab[dom], "avg_launch_us": round(kinfo[dom]["avg_us"], 2)}
+            # the same figure on SURVEY.md section 8(d)'s terms for the two blend kernels (K7: 52 P + 116 D + 228 N + 216 R^2, K6:
+            # 116 D + 72 R^2 + 40 P + 8 T -- whole lists and the whole texture, where this file's own definition counts the list up to
+            # the last contributor and the texels actually touched: the smaller, stricter number stays `achieved`)
+            sv = {"render_bwd": 52 * P + 116 * s.D + 228 * N + 216 * R * R, "render_fwd": 116 * s.D + 72 * R * R + 40 * P + 8 * T}.get(dom)
+            if sv and not untextured:
+                roofline["alg_bytes_per_launch_survey_8d"] = sv
+                roofline["frac_survey_8d"] = round(sv / (kinfo[dom]["avg_us"] * 1e-6) / 1e9 / HBM_PEAK_GBS, 5)
+            if traffic_all:
+                # every kernel group's measured past-L2 traffic per view beside its algorithmic bytes (VERDICT r5 #3 iii): the ratio is
+                # what the gather / scatter access patterns cost on top of the compulsory bytes
+                tb = {k: {"traffic_MB": round(v["traffic_bytes"] / 1e6, 1), "alg_MB": round(ab.get(k, 0) / 1e6, 1),
+                          "traffic_over_alg": (round(v["traffic_bytes"] / ab[k], 2) if ab.get(k) else None)} for k, v in traffic_all.items()}
+                ttot = sum(v["traffic_bytes"] for v in traffic_all.values())
+                roofline["traffic_by_kernel_per_view"] = tb
+                roofline["traffic_total_per_view_MB"] = round(ttot / 1e6, 1)
+                roofline["traffic_total_over_alg"] = round(ttot / max(sum(ab.values()), 1), 2)
+                roofline["traffic_rate_at_value_GBps"] = round(ttot * value / world / 1e9, 1)
+            if dom == DOMINANT and kern_solo_dom[1]:
+                solo_us = 1e3 * kern_solo_dom[0] / kern_solo_dom[1]
+                roofline["solo_launch_us"] = round(solo_us, 2)
+                roofline["solo_frac"] = round(ab[dom] / (solo_us * 1e-6) / 1e9 / HBM_PEAK_GBS, 5)
+                if args.streams > 1:
+                    roofline["note"] = (f"achieved / frac use the launch duration inside the timed region, where {args.streams} views are in "
+                                        "flight on separate HIP streams and the kernel shares the GPU with other views' kernels; solo_* is "
+                                        "the same kernel with the views run one after the other (extra steps after the timed region)")
+        view_bytes = sum(ab[k] for k in ab if (with_bwd or k not in ("render_bwd", "preprocess_bwd")))
 
-    # same-run measured HBM ceiling: device-to-device copy of 1 GiB, read + write bytes
-    hbm_measured = None
-    if rank == 0:
-        try:
-            src = torch.empty(1 << 28, dtype=torch.float32, device=dev)
-            dst = torch.empty_like(src)
-            for _ in range(2):
-                dst.copy_(src)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(5):
-                dst.copy_(src)
-            e1.record()
-            torch.cuda.synchronize(dev)
-            hbm_measured = round(5 * 2 * src.numel() * 4 / (e0.elapsed_time(e1) * 1e-3) / 1e9, 1)
-            del src, dst
-        except Exception:
-            hbm_measured = None
+        # same-run measured HBM ceiling: device-to-device copy of 1 GiB, read + write bytes
+        hbm_measured = None
+        if rank == 0:
+            try:
+                src = torch.empty(1 << 28, dtype=torch.float32, device=dev)
+                dst = torch.empty_like(src)
+                for _ in range(2):
+                    dst.copy_(src)
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(5):
+                    dst.copy_(src)
+                e1.record()
+                torch.cuda.synchronize(dev)
+                hbm_measured = round(5 * 2 * src.numel() * 4 / (e0.elapsed_time(e1) * 1e-3) / 1e9, 1)
+                del src, dst
+            except Exception:
+                hbm_measured = None
 
-    # ---- the same workload through the reference-compatible call pattern: activation OUTPUTS as operator
-    # inputs, a fresh non-leaf means2D per view, plain autograd (no grad_sink) -- what render/uv_tex_render.py does.
-    compat = None
-    ref_iter = None
-    if rank == 0 and with_bwd and not args.no_kernel_table and not args.no_extra_legs and not untextured:
-        raw = {n: leaves[n].detach().clone().requires_grad_(True) for n in names}
-        raw["scales"] = leaves["scales"].detach().log().requires_grad_(True)
-        op = leaves["opacities"].detach().clamp(1e-6, 1 - 1e-6)
-        raw["opacities"] = torch.log(op / (1 - op)).requires_grad_(True)
+        # ---- the same workload through the reference-compatible call pattern: activation OUTPUTS as operator
+        # inputs, a fresh non-leaf means2D per view, plain autograd (no grad_sink) -- what render/uv_tex_render.py does.
+        compat = None
+        ref_iter = None
+        if rank == 0 and with_bwd and not args.no_kernel_table and not args.no_extra_legs and not untextured:
+            raw = {n: leaves[n].detach().clone().requires_grad_(True) for n in names}
+            raw["scales"] = leaves["scales"].detach().log().requires_grad_(True)
+            op = leaves["opacities"].detach().clamp(1e-6, 1 - 1e-6)
+            raw["opacities"] = torch.log(op / (1 - op)).requires_grad_(True)
 
-        compat_settings = {v: settings(cams[v]) for v in my_views[:max(4, min(16, len(my_views)))]}     # the reference's cameras
-        # live on the GPU (utils/cameras.py:62-65); the rasterizer module itself is built per call (render/uv_tex_render.py:40)
+            compat_settings = {v: settings(cams[v]) for v in my_views[:max(4, min(16, len(my_views)))]}     # the reference's cameras
+            # live on the GPU (utils/cameras.py:62-65); the rasterizer module itself is built per call (render/uv_tex_render.py:40)
 
-        def compat_view(v):
-            m2 = torch.zeros_like(raw["means3D"], requires_grad=True) + 0
-            m2.retain_grad()
-            out = GaussianRasterizer(compat_settings[v])(
-                means3D=raw["means3D"], means2D=m2, shs=raw["shs"], opacities=torch.sigmoid(raw["opacities"]),
-                scales=torch.exp(raw["scales"]), rotations=torch.nn.functional.normalize(raw["rotations"]),
-                uvs=raw["uvs"], gradient_uvs=juv, texture=raw["texture"], extra_attrs=None)
-            torch.autograd.backward([out[0], out[3], out[2]], [g_img, g_alpha, g_norm])
-            for p_ in raw.values():          # optimizer.zero_grad(set_to_none=True) after every iteration (models/texture_gaussian3d.py:442-444)
-                p_.grad = None
-        nv = min(16, len(my_views))
-        for v in my_views[:4]:
-            compat_view(v)
-        torch.cuda.synchronize(dev)
-        c0 = time.perf_counter()
-        for v in my_views[:nv]:
-            compat_view(v)
-        torch.cuda.synchronize(dev)
-        compat = {"views_per_s": round(nv / (time.perf_counter() - c0), 2), "views": nv,
-                  "note": "one view per call through autograd: sigmoid/exp/normalize activations + their backward, fresh "
-                          "means2D, gradients delivered by autograd (no fused sink) and dropped with set_to_none after every view as "
-                          "models/texture_gaussian3d.py:442-444 does (until round 5 they were left to accumulate: an extra "
-                          "read-modify-write of 150 MB per view the reference does not pay); measured after the timed region"}
-
-        # ---- the reference's ITERATION after iteration 10 000 (models/texture_gaussian3d.py:318, 375-389, 410): render at the active
-        # degree, render AGAIN at sh_degree 0 (lambda_no_sh: same camera, same Gaussians, activations recomputed by the getters),
-        # one backward of both losses.  With the shared-geometry path the second render is K1 + K6 on the first one's lists.
-        from texgs import rasterizer as RZ
-        st_pairs = {v: (compat_settings[v], compat_settings[v]._replace(sh_degree=0)) for v in compat_settings}
-
-        def ref_iteration(v):
-            outs = []
-            for st_ in st_pairs[v]:
+            def compat_view(v):
                 m2 = torch.zeros_like(raw["means3D"], requires_grad=True) + 0
                 m2.retain_grad()
-                outs.append(GaussianRasterizer(st_)(
+                out = GaussianRasterizer(compat_settings[v])(
                     means3D=raw["means3D"], means2D=m2, shs=raw["shs"], opacities=torch.sigmoid(raw["opacities"]),
                     scales=torch.exp(raw["scales"]), rotations=torch.nn.functional.normalize(raw["rotations"]),
-                    uvs=raw["uvs"], gradient_uvs=juv, texture=raw["texture"], extra_attrs=None))
-            torch.autograd.backward([outs[0][0], outs[0][3], outs[0][2], outs[1][0]], [g_img, g_alpha, g_norm, 2.0 * g_img])
-            for p_ in raw.values():
-                p_.grad = None
-        ref_iter = {}
-        saved_gc = RZ.GEOM_CACHE
-        for label, on in (("separate_geometry", False), ("shared_geometry", True)):
-            RZ.GEOM_CACHE = on
-            RZ.release_scratch(dev)
-            vs = list(compat_settings)[:nv]
-            for v in vs[:3]:
-                ref_iteration(v)
+                    uvs=raw["uvs"], gradient_uvs=juv, texture=raw["texture"], extra_attrs=None)
+                torch.autograd.backward([out[0], out[3], out[2]], [g_img, g_alpha, g_norm])
+                for p_ in raw.values():          # optimizer.zero_grad(set_to_none=True) after every iteration (models/texture_gaussian3d.py:442-444)
+                    p_.grad = None
+            nv = min(16, len(my_views))
+            for v in my_views[:4]:
+                compat_view(v)
             torch.cuda.synchronize(dev)
             c0 = time.perf_counter()
-            for v in vs:
-                ref_iteration(v)
+            for v in my_views[:nv]:
+                compat_view(v)
             torch.cuda.synchronize(dev)
-            ref_iter[label + "_ms_per_iteration"] = round(1e3 * (time.perf_counter() - c0) / len(vs), 4)
-        RZ.GEOM_CACHE = saved_gc
-        ref_iter["iterations"] = nv
-        ref_iter["note"] = ("2 renders (sh_degree 3, then 0) + 1 backward per iteration through plain autograd, one view per iteration; "
-                            "shared = the second render re-uses the first one's tile / survivor lists (K1 geometry fingerprint)")
-        del raw
+            compat = {"views_per_s": round(nv / (time.perf_counter() - c0), 2), "views": nv,
+                      "note": "one view per call through autograd: sigmoid/exp/normalize activations + their backward, fresh "
+                              "means2D, gradients delivered by autograd (no fused sink) and dropped with set_to_none after every view as "
+                              "models/texture_gaussian3d.py:442-444 does (until round 5 they were left to accumulate: an extra "
+                              "read-modify-write of 150 MB per view the reference does not pay); measured after the timed region"}
 
-    # ---- forward-only callers that build a graph (retexture.py:27, visual_step: parameters require grad, backward never runs)
-    retex = None
-    if rank == 0 and not with_bwd and not args.no_kernel_table and not args.no_extra_legs and not untextured:
-        from texgs import rasterizer as RZ
-        saved_gc = RZ.GEOM_CACHE
-        RZ.GEOM_CACHE = False               # (every frame here is a different view anyway)
-        vs = my_views[:min(32, len(my_views))]
-        res = {}
-        for label, rg in (("no_grad_inputs", False), ("inputs_require_grad", True)):
-            lv = {n: leaves[n].detach().clone().requires_grad_(rg) for n in names}
+            # ---- the reference's ITERATION after iteration 10 000 (models/texture_gaussian3d.py:318, 375-389, 410): render at the active
+            # degree, render AGAIN at sh_degree 0 (lambda_no_sh: same camera, same Gaussians, activations recomputed by the getters),
+            # one backward of both losses.  With the shared-geometry path the second render is K1 + K6 on the first one's lists.
+            from texgs import rasterizer as RZ
+            st_pairs = {v: (compat_settings[v], compat_settings[v]._replace(sh_degree=0)) for v in compat_settings}
 
-            def frame_(v):
-                out = GaussianRasterizer(settings(cams[v]))(means3D=lv["means3D"], means2D=None, shs=lv["shs"], opacities=lv["opacities"],
-                                                            scales=lv["scales"], rotations=lv["rotations"], uvs=lv["uvs"],
-                                                            gradient_uvs=juv, texture=lv["texture"], extra_attrs=None)
-                return out[0]
-            for v in vs[:4]:
-                frame_(v)
-            torch.cuda.synchronize(dev)
-            c0 = time.perf_counter()
-            for v in vs:
-                frame_(v)
-            torch.cuda.synchronize(dev)
-            res[label + "_views_per_s"] = round(len(vs) / (time.perf_counter() - c0), 1)
-        RZ.GEOM_CACHE = saved_gc
-        res["ratio"] = round(res["inputs_require_grad_views_per_s"] / res["no_grad_inputs_views_per_s"], 4)
-        res["note"] = ("views one after the other on one stream, a new rasterizer module per frame as render/uv_tex_render.py:40 builds; "
-                       "with inputs that require grad the forward leaves K6's hand-off to a backward that never comes (LAZY_HANDOFF)")
-        retex = res
+            def ref_iteration(v):
+                outs = []
+                for st_ in st_pairs[v]:
+                    m2 = torch.zeros_like(raw["means3D"], requires_grad=True) + 0
+                    m2.retain_grad()
+                    outs.append(GaussianRasterizer(st_)(
+                        means3D=raw["means3D"], means2D=m2, shs=raw["shs"], opacities=torch.sigmoid(raw["opacities"]),
+                        scales=torch.exp(raw["scales"]), rotations=torch.nn.functional.normalize(raw["rotations"]),
+                        uvs=raw["uvs"], gradient_uvs=juv, texture=raw["texture"], extra_attrs=None))
+                torch.autograd.backward([outs[0][0], outs[0][3], outs[0][2], outs[1][0]], [g_img, g_alpha, g_norm, 2.0 * g_img])
+                for p_ in raw.values():
+                    p_.grad = None
+            ref_iter = {}
+            saved_gc = RZ.GEOM_CACHE
+            for label, on in (("separate_geometry", False), ("shared_geometry", True)):
+                RZ.GEOM_CACHE = on
+                RZ.release_scratch(dev)
+                vs = list(compat_settings)[:nv]
+                for v in vs[:3]:
+                    ref_iteration(v)
+                torch.cuda.synchronize(dev)
+                c0 = time.perf_counter()
+                for v in vs:
+                    ref_iteration(v)
+                torch.cuda.synchronize(dev)
+                ref_iter[label + "_ms_per_iteration"] = round(1e3 * (time.perf_counter() - c0) / len(vs), 4)
+            RZ.GEOM_CACHE = saved_gc
+            ref_iter["iterations"] = nv
+            ref_iter["note"] = ("2 renders (sh_degree 3, then 0) + 1 backward per iteration through plain autograd, one view per iteration; "
+                                "shared = the second render re-uses the first one's tile / survivor lists (K1 geometry fingerprint)")
+            del raw
 
-    cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        cpu = cpu_baseline(scene, cams[my_views[0]], W, H, with_bwd)
+        # ---- forward-only callers that build a graph (retexture.py:27, visual_step: parameters require grad, backward never runs)
+        retex = None
+        if rank == 0 and not with_bwd and not args.no_kernel_table and not args.no_extra_legs and not untextured:
+            from texgs import rasterizer as RZ
+            saved_gc = RZ.GEOM_CACHE
+            RZ.GEOM_CACHE = False               # (every frame here is a different view anyway)
+            vs = my_views[:min(32, len(my_views))]
+            res = {}
+            for label, rg in (("no_grad_inputs", False), ("inputs_require_grad", True)):
+                lv = {n: leaves[n].detach().clone().requires_grad_(rg) for n in names}
+
+                def frame_(v):
+                    out = GaussianRasterizer(settings(cams[v]))(means3D=lv["means3D"], means2D=None, shs=lv["shs"], opacities=lv["opacities"],
+                                                                scales=lv["scales"], rotations=lv["rotations"], uvs=lv["uvs"],
+                                                                gradient_uvs=juv, texture=lv["texture"], extra_attrs=None)
+                    return out[0]
+                for v in vs[:4]:
+                    frame_(v)
+                torch.cuda.synchronize(dev)
+                c0 = time.perf_counter()
+                for v in vs:
+                    frame_(v)
+                torch.cuda.synchronize(dev)
+                res[label + "_views_per_s"] = round(len(vs) / (time.perf_counter() - c0), 1)
+            RZ.GEOM_CACHE = saved_gc
+            res["ratio"] = round(res["inputs_require_grad_views_per_s"] / res["no_grad_inputs_views_per_s"], 4)
+            res["note"] = ("views one after the other on one stream, a new rasterizer module per frame as render/uv_tex_render.py:40 builds; "
+                           "with inputs that require grad the forward leaves K6's hand-off to a backward that never comes (LAZY_HANDOFF)")
+            retex = res
+
+        cpu = None
+        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+            cpu = cpu_baseline(scene, cams[my_views[0]], W, H, with_bwd)
 
     if rank == 0:
         line = {
@@ -602,14 +679,16 @@ def main():
                        if (args.workload == "c3" and not args.tex_res) else f"{mode} views/sec ({args.workload}" + (f", R={R}" if args.tex_res else "") + ")") if not untextured
                       else f"{mode} views/sec ({args.workload}, untextured diff_gauss surface)",
             "value": round(value, 3), "unit": "views/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "value_long": round(value_long, 3),
-            "value_long_note": f"the same step loop run again for {long_elapsed:.2f} s ({long_steps} steps) after the timed region",
+            "full": args.full,
+            "value_long": round(value_long, 3) if args.full else None,
+            "value_long_note": (f"the same step loop run again for {long_elapsed:.2f} s ({long_steps} steps) after the timed region"
+                                if args.full else "--full only"),
             "build_id": _lib.BUILD_ID,
             "ms_per_step": round(1e3 * elapsed / args.steps, 4), "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "config": {"workload": f"{args.workload}: N={N} Gaussians, cubemap 6x{R}x{R}x3 f32, {W}x{H}, {mode}, sh_degree 3",
                        "views_per_step_per_gpu": args.views_per_step, "global_views_per_step": args.views_per_step * world,
-                       "num_rendered_D": s.D, "D_eff": D_eff, "parallelism": f"views sharded dp{world}",
+                       "num_rendered_D": s.D if args.full else None, "D_eff": D_eff, "parallelism": f"views sharded dp{world}",
                        "view_pipeline": (f"{args.streams} HIP streams, order={args.order}"
                                          + (", forwards begun one view per stream ahead" if (args.prefetch and not untextured and with_bwd) else ""))
                        if args.streams > 1 else "serial",
@@ -630,14 +709,14 @@ def main():
             "reference_iteration": ref_iter,
             "retexture_pattern": retex,
             "alg_bytes_per_view": view_bytes,
-            "pipeline_GBps": round(view_bytes * value / world / 1e9, 2),
-            "pipeline_frac_of_hbm_peak": round(view_bytes * value / world / 1e9 / HBM_PEAK_GBS, 5),
+            "pipeline_GBps": round(view_bytes * value / world / 1e9, 2) if args.full else None,
+            "pipeline_frac_of_hbm_peak": round(view_bytes * value / world / 1e9 / HBM_PEAK_GBS, 5) if args.full else None,
             "hbm_copy_ceiling_GBps_measured": hbm_measured,
             "roofline": roofline,
             "kernels": {k: {kk: (round(vv, 2) if isinstance(vv, float) else vv) for kk, vv in v.items()}
-                        for k, v in kinfo.items()},
-            "kernels_note": f"{DOMINANT}: HIP events inside the (pipelined) timed region; the others: two extra fully bracketed "
-                            "steps after it, views one after the other on one stream",
+                        for k, v in kinfo.items()} if args.full else None,
+            "kernels_note": (f"{DOMINANT}: HIP events inside the (pipelined) timed region; the others: two extra fully bracketed "
+                             "steps after it, views one after the other on one stream") if args.full else "--full only",
             "cpu_baseline": cpu,
         }
         print(json.dumps(line), flush=True)

@@ -1,10 +1,12 @@
 #!/bin/bash
 # usage (GPU box): scripts/r4_ab.sh lib1.so lib2.so ...   -- C3 bench per library: serial kernel table + pipelined views/s
-cd $GRAFT_REPO_ROOT
-mkdir -p gpurun_out
+R=$(cd "$(dirname "$0")/.." && pwd)
+O=${TEXGS_OUT:-$R/out}
+cd "$R"
+mkdir -p "$O"
 for V in "$@"; do
 for MODE in "--streams 1" ""; do
-TEXGS_LIB=$GRAFT_REPO_ROOT/texture-gs_amd/$V timeout 400 python bench.py --no-cpu-baseline --steps 8 --warmup 3 $MODE 2> gpurun_out/ab_err.log | python -c "
+TEXGS_LIB=$R/texture-gs_amd/$V timeout 400 python bench.py --full --no-cpu-baseline --steps 8 --warmup 3 $MODE 2> $O/ab_err.log | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):
@@ -12,4 +14,4 @@ for l in sys.stdin:
 "
 done
 done
-tail -3 gpurun_out/ab_err.log
+tail -3 $O/ab_err.log

@@ -1,9 +1,10 @@
 #!/bin/bash
 # usage (GPU box): scripts/r4_pipe.sh "<bench args>" lib1.so lib2.so ...  -- pipelined C3 views/s per library (no kernel table)
-cd $GRAFT_REPO_ROOT
+R=$(cd "$(dirname "$0")/.." && pwd)
+cd "$R"
 A=$1; shift
 for V in "$@"; do
-TEXGS_LIB=$GRAFT_REPO_ROOT/texture-gs_amd/$V timeout 300 python bench.py --no-cpu-baseline --no-kernel-table --steps 15 --warmup 4 $A 2>/dev/null | python -c "
+TEXGS_LIB=$R/texture-gs_amd/$V timeout 300 python bench.py --full --no-cpu-baseline --no-kernel-table --steps 15 --warmup 4 $A 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -3,7 +3,7 @@
 # serial one (separate runs, as required; PMC collection serialises the kernels anyway).
 cd /tmp && export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-/root/repo}
-OUT=$R/gpurun_out/prof
+OUT=${TEXGS_OUT:-$R/out}/prof
 rm -rf $OUT; mkdir -p $OUT
 PIPE="--steps 6 --warmup 3 --no-cpu-baseline --no-kernel-table"
 SER="--steps 3 --warmup 3 --no-cpu-baseline --no-kernel-table --streams 1"

@@ -16,7 +16,7 @@ no source) travel to the GPU box, the reference does not.
   norm_from_depth.npz  losses/norm_reg_loss.py norm_from_depth (pseudo-normal + mask of a depth map) and norm_reg_loss with its
                autograd gradient w.r.t. the predicted normal, two cameras from utils/graphics.py getWorld2View2
   host_terms.npz  losses/zero_one_loss.py zero_one_loss (value + autograd gradient, both clamps hit) and
-               TextureGaussian3D.depth2world (models/texture_gaussian3d.py:299-309) on a random depth map
+               TextureGaussian3D.depth2world (models/texture_gaussian3d.py:299-309) on a random depth map, in fp32 and float64
   uvnet.npz    models/modules/uv_net.py UVNet with models/modules/utils.py build_nn_network (the `use_tcnn: False` path; utils.py
                imports tinycudann at top level, so the class / function definitions are taken from the two sources with `ast`
                and RUN): weights, embedding, 64 points, uvs, and the Jacobian exactly as
@@ -224,7 +224,10 @@ def host_terms():
     full = (wvt.unsqueeze(0).bmm(proj.unsqueeze(0))).squeeze(0)
     depth = 2.0 + torch.rand(17, 23, generator=g)
     xyz = ns["depth2world"](None, depth, full, zfar, znear)
+    # the same function in float64: the fp32 result above depends on the host's BLAS path (4x4 inverse, cond ~1.5e3)
+    xyz64 = ns["depth2world"](None, depth.double(), full.double(), zfar, znear)
     out.update(d2w_depth=depth.numpy(), d2w_full_proj=full.numpy(), d2w_zfar=zfar, d2w_znear=znear, d2w_xyz=xyz.numpy(),
+               d2w_xyz64=xyz64.numpy(),
                d2w_wvt=wvt.numpy(), d2w_fov=np.array([fovx, fovy]))
     np.savez_compressed(os.path.join(HERE, "host_terms.npz"), **out)
 
