@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define TEXGS_ABI_VERSION 15
+#define TEXGS_ABI_VERSION 16
 #define TEXGS_TILE 16          /* 16x16 pixel tiles, one 256-thread workgroup (4 wave64) per tile     */
 #define TEXGS_REC_TEST_FLOATS 8    /* per-Gaussian TEST record (32 B): what the per-block culls and the alpha test read  */
 #define TEXGS_REC_SHADE_FLOATS 20  /* per-Gaussian SHADING record (80 B): fetched only for Gaussians that survive a cull (one record per
@@ -399,6 +399,40 @@ int texgs_uv_backward(const TexGSUVNet* net, const float* xyz, const float* g_uv
  * of the forward launch bit for bit (v15; same arguments and temp size). */
 int texgs_uv_backward_mixed(const TexGSUVNet* net, const float* xyz, const float* g_uvs, int32_t N, const TexGSUVNetGrad* out, void* temp,
                             void* stream);
+
+/* ---- UV-map stage (v16): models/uv_map_gaussian3d.py:167-238 ----
+ * Multiresolution hash-grid encoding of InvUVNet (tiny-cuda-nn "HashGrid", models/modules/utils.py:5-29; index rules restated
+ * from the published grid encoding, UNPINNED -- DESIGN.md section 10).  For level l:
+ *   scale_l = exp2f(l * log2f(per_level_scale)) * base_resolution - 1,  res_l = ceil(scale_l) + 1,
+ *   size_l = min(roundup8(res_l^3), 2^log2_hashmap_size),  offset_l = sum_{k<l} size_k  (rows of n_features floats);
+ * a corner p of the cell of pos = scale_l * x + 0.5 is p0 + p1 res + p2 res^2 when res_l^3 <= size_l, else the xor-prime hash
+ * p0 ^ p1 * 2654435761 ^ p2 * 805459861 (uint32), then % size_l; trilinear weights.  x is not clamped. */
+#define TEXGS_HASHGRID_MAX_LEVELS 16
+#define TEXGS_HASHGRID_FEATURES 4      /* n_features must be 4 */
+typedef struct TexGSHashGrid {
+    int32_t n_levels;              /* L, 1..TEXGS_HASHGRID_MAX_LEVELS */
+    int32_t n_features;            /* F = 4 */
+    int32_t log2_hashmap_size;     /* 1..24 */
+    float   base_resolution;       /* >= 1 */
+    float   per_level_scale;       /* in [1, 16] */
+} TexGSHashGrid;
+/* HOST: the level table (arrays of n_levels entries, any may be NULL) and the parameter count L-sum(size_l) * F. */
+int texgs_hashgrid_levels(const TexGSHashGrid* grid, float* scale, uint32_t* res, uint32_t* size, uint32_t* offset, uint32_t* n_params);
+/* enc f32[N, L*F] (row i: level l at columns l*F .. l*F+F-1) from params f32[n_params] and x f32[N, 3].  The caller guarantees
+ * the sizes (the library cannot see them).  params, enc, d_enc and d_params are read / written as 16-byte rows: they must be
+ * 16-byte aligned (checked; an error otherwise). */
+int texgs_hashgrid_forward(const TexGSHashGrid* grid, const float* params, const float* x, int32_t N, float* enc, void* stream);
+/* Backward for an upstream d_enc f32[N, L*F]: d_params f32[n_params] is ACCUMULATED into (NULL: skipped); d_x f32[N, 3] is
+ * OVERWRITTEN (NULL: skipped).  A level whose gradient slab (size_l x 16 B) fits in 64 KiB is accumulated in LDS per workgroup
+ * and flushed with contiguous global float atomics; other levels add with one global float atomic per corner and feature.
+ * temp: texgs_hashgrid_backward_temp_bytes(grid, N) bytes (the per-level shares of d_x). */
+size_t texgs_hashgrid_backward_temp_bytes(const TexGSHashGrid* grid, int32_t N);
+int texgs_hashgrid_backward(const TexGSHashGrid* grid, const float* params, const float* x, const float* d_enc, int32_t N,
+                            float* d_params, float* d_x, void* temp, void* stream);
+/* Nearest neighbour of every a_i (f32[P, 3]) in b (f32[Q, 3], Q >= 1): d2[i] = min_j sum_d (a_id - b_jd)^2, idx[i] = that j, the
+ * lowest j among equal distances.  A point with no finite distance gets d2 = NaN, idx = 0.  temp: texgs_chamfer_nn_temp_bytes(P). */
+size_t texgs_chamfer_nn_temp_bytes(int32_t P);
+int texgs_chamfer_nn(const float* a, int32_t P, const float* b, int32_t Q, float* d2, int32_t* idx, void* temp, void* stream);
 
 /* Hardware self-test of the wave64 cross-lane primitives the backward's reductions use (csrc/wave_ops.h: DPP lane^4 /
  * lane^8 exchanges, permlane16/32 swaps, both transposing butterflies).  seed: f32[128] device; out: f32[576] device,

@@ -27,6 +27,7 @@ UNITS = {
     "loss.hip": [],
     "selftest.hip": [],
     "uvnet.hip": [],
+    "uvmap.hip": ["-munsafe-fp-atomics"],
     "abi.hip": [],
 }
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "wave_ops.h"), os.path.join(CSRC, "render_bwd_body.h"),

@@ -484,6 +484,83 @@ int texgs_uv_backward_mixed(const TexGSUVNet* net, const float* xyz, const float
     return uv_backward_impl(net, xyz, g_uvs, N, out, temp, 1, stream);
 }
 
+static int check_hashgrid(const TexGSHashGrid* g, uint32_t* n_params) {
+    if (!g) return fail_msg("grid is NULL");
+    float sc[TEXGS_HASHGRID_MAX_LEVELS];
+    uint32_t r[TEXGS_HASHGRID_MAX_LEVELS], sz[TEXGS_HASHGRID_MAX_LEVELS], off[TEXGS_HASHGRID_MAX_LEVELS];
+    switch (hashgrid_levels(g, sc, r, sz, off, n_params)) {
+    case 0: return 0;
+    case -1: return fail_msg("hash grid: n_levels must be in [1, 16]");
+    case -2: return fail_msg("hash grid: n_features must be 4");
+    case -3: return fail_msg("hash grid: log2_hashmap_size must be in [1, 24]");
+    case -4: return fail_msg("hash grid: base_resolution must be >= 1 and per_level_scale in [1, 16]");
+    case -5: return fail_msg("hash grid: a level's resolution is out of range");
+    default: return fail_msg("hash grid: more than 2^31 parameters");
+    }
+}
+
+int texgs_hashgrid_levels(const TexGSHashGrid* grid, float* scale, uint32_t* res, uint32_t* size, uint32_t* offset, uint32_t* n_params) {
+    uint32_t n = 0;
+    if (int r = check_hashgrid(grid, &n)) return r;
+    float sc[TEXGS_HASHGRID_MAX_LEVELS];
+    uint32_t rs[TEXGS_HASHGRID_MAX_LEVELS], sz[TEXGS_HASHGRID_MAX_LEVELS], off[TEXGS_HASHGRID_MAX_LEVELS];
+    hashgrid_levels(grid, sc, rs, sz, off, &n);
+    for (int l = 0; l < grid->n_levels; ++l) {
+        if (scale) scale[l] = sc[l];
+        if (res) res[l] = rs[l];
+        if (size) size[l] = sz[l];
+        if (offset) offset[l] = off[l];
+    }
+    if (n_params) *n_params = n;
+    return 0;
+}
+
+int texgs_hashgrid_forward(const TexGSHashGrid* grid, const float* params, const float* x, int32_t N, float* enc, void* stream) {
+    uint32_t n = 0;
+    if (int r = check_hashgrid(grid, &n)) return r;
+    if (N < 0) return fail_msg("N < 0");
+    if ((int64_t)N * grid->n_levels * TEXGS_HASHGRID_FEATURES > INT32_MAX) return fail_msg("N * L * F >= 2^31");
+    if (N > 0 && (!params || !x || !enc)) return fail_msg("NULL argument");
+    if (N > 0 && (((uintptr_t)params | (uintptr_t)enc) & 15)) return fail_msg("params and enc must be 16-byte aligned");
+    if (int r = launch_hashgrid_forward(grid, params, x, N, enc, (hipStream_t)stream)) return fail("hashgrid_forward", (hipError_t)r);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : fail("hashgrid_forward", e);
+}
+
+size_t texgs_hashgrid_backward_temp_bytes(const TexGSHashGrid* grid, int32_t N) {
+    uint32_t n = 0;
+    if (!grid || check_hashgrid(grid, &n)) return 0;
+    return hashgrid_backward_temp_bytes(grid, N);
+}
+
+int texgs_hashgrid_backward(const TexGSHashGrid* grid, const float* params, const float* x, const float* d_enc, int32_t N,
+                            float* d_params, float* d_x, void* temp, void* stream) {
+    uint32_t n = 0;
+    if (int r = check_hashgrid(grid, &n)) return r;
+    if (N < 0) return fail_msg("N < 0");
+    if ((int64_t)N * grid->n_levels * TEXGS_HASHGRID_FEATURES > INT32_MAX) return fail_msg("N * L * F >= 2^31");
+    if (N > 0 && (!params || !x || !d_enc)) return fail_msg("NULL argument");
+    if (N > 0 && (((uintptr_t)params | (uintptr_t)d_enc | (uintptr_t)d_params) & 15))
+        return fail_msg("params, d_enc and d_params must be 16-byte aligned");
+    if (N > 0 && d_x && !temp) return fail_msg("temp is NULL (d_x needs texgs_hashgrid_backward_temp_bytes)");
+    if (int r = launch_hashgrid_backward(grid, params, x, d_enc, N, d_params, d_x, temp, (hipStream_t)stream))
+        return fail("hashgrid_backward", (hipError_t)r);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : fail("hashgrid_backward", e);
+}
+
+size_t texgs_chamfer_nn_temp_bytes(int32_t P) { return chamfer_nn_temp_bytes(P); }
+
+int texgs_chamfer_nn(const float* a, int32_t P, const float* b, int32_t Q, float* d2, int32_t* idx, void* temp, void* stream) {
+    if (P < 0) return fail_msg("P < 0");
+    if (Q < 1) return fail_msg("the reference set is empty (Q < 1)");
+    if ((int64_t)Q > 65535ll * 512) return fail_msg("Q > 65535 * 512");
+    if (P > 0 && (!a || !b || !d2 || !idx || !temp)) return fail_msg("NULL argument");
+    if (int r = launch_chamfer_nn(a, P, b, Q, d2, idx, temp, (hipStream_t)stream)) return fail("chamfer_nn", (hipError_t)r);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : fail("chamfer_nn", e);
+}
+
 int texgs_selftest_waveops(const float* seed128, float* out576, void* stream) {
     if (!seed128 || !out576) return fail_msg("NULL argument");
     launch_selftest_waveops(seed128, out576, (hipStream_t)stream);

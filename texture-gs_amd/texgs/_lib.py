@@ -6,7 +6,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TEXGS_LIB") or os.path.join(os.path.dirname(_HERE), "libtexgs.so")   # TEXGS_LIB: experiment builds only
 
-ABI_VERSION = 15
+ABI_VERSION = 16
 ERR_CAPACITY = 1000
 TILE = 16
 REC_TEST_FLOATS = 8
@@ -67,6 +67,15 @@ class UVNetStruct(C.Structure):
         + [("hidden", C.c_int32)]
 
 
+class HashGridStruct(C.Structure):
+    _fields_ = [("n_levels", C.c_int32), ("n_features", C.c_int32), ("log2_hashmap_size", C.c_int32), ("base_resolution", C.c_float),
+                ("per_level_scale", C.c_float)]
+
+
+HASHGRID_MAX_LEVELS = 16
+HASHGRID_FEATURES = 4
+
+
 class UVNetGradStruct(C.Structure):
     _fields_ = [(n, _fp) for n in ("dW1", "db1", "dW2", "db2", "dW3", "db3", "dW4", "db4", "dW5", "db5")]
 
@@ -76,7 +85,9 @@ EXPORTS = ["texgs_abi_version", "texgs_build_id", "texgs_last_error", "texgs_sca
            "texgs_render_forward", "texgs_forward", "texgs_backward", "texgs_backward_render", "texgs_backward_preprocess",
            "texgs_rgb_alpha_loss", "texgs_mark_visible", "texgs_profile_enable", "texgs_tex_bin_count",
            "texgs_profile_read", "texgs_profile_select", "texgs_selftest_waveops", "texgs_geom_losses", "texgs_norm_from_depth", "texgs_uv_taylor", "texgs_uv_taylor_temp_bytes", "texgs_uv_pack", "texgs_uv_taylor_packed",
-           "texgs_uv_pack_bf16x3", "texgs_uv_taylor_packed_bf16x3", "texgs_uv_backward", "texgs_uv_backward_mixed", "texgs_uv_backward_temp_bytes", "texgs_uv_pack_mixed", "texgs_uv_taylor_packed_mixed"]
+           "texgs_uv_pack_bf16x3", "texgs_uv_taylor_packed_bf16x3", "texgs_uv_backward", "texgs_uv_backward_mixed", "texgs_uv_backward_temp_bytes", "texgs_uv_pack_mixed", "texgs_uv_taylor_packed_mixed",
+           "texgs_hashgrid_levels", "texgs_hashgrid_forward", "texgs_hashgrid_backward_temp_bytes", "texgs_hashgrid_backward",
+           "texgs_chamfer_nn_temp_bytes", "texgs_chamfer_nn"]
 KERNEL_NAMES = ["preprocess_fwd", "scan", "duplicate", "sort", "ranges", "render_fwd", "render_bwd", "preprocess_bwd",
                 "texgrad_reduce"]
 
@@ -152,6 +163,19 @@ def load():
     lib.texgs_uv_backward.restype = C.c_int
     lib.texgs_uv_backward_mixed.argtypes = lib.texgs_uv_backward.argtypes
     lib.texgs_uv_backward_mixed.restype = C.c_int
+    lib.texgs_hashgrid_levels.argtypes = [P(HashGridStruct), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, P(C.c_uint32)]
+    lib.texgs_hashgrid_levels.restype = C.c_int
+    lib.texgs_hashgrid_forward.argtypes = [P(HashGridStruct), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.texgs_hashgrid_forward.restype = C.c_int
+    lib.texgs_hashgrid_backward_temp_bytes.argtypes = [P(HashGridStruct), C.c_int32]
+    lib.texgs_hashgrid_backward_temp_bytes.restype = C.c_size_t
+    lib.texgs_hashgrid_backward.argtypes = [P(HashGridStruct), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p]
+    lib.texgs_hashgrid_backward.restype = C.c_int
+    lib.texgs_chamfer_nn_temp_bytes.argtypes = [C.c_int32]
+    lib.texgs_chamfer_nn_temp_bytes.restype = C.c_size_t
+    lib.texgs_chamfer_nn.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.texgs_chamfer_nn.restype = C.c_int
     lib.texgs_selftest_waveops.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     lib.texgs_selftest_waveops.restype = C.c_int
     lib.texgs_profile_enable.argtypes = [C.c_int]
