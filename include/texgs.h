@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define TEXGS_ABI_VERSION 16
+#define TEXGS_ABI_VERSION 17
 #define TEXGS_TILE 16          /* 16x16 pixel tiles, one 256-thread workgroup (4 wave64) per tile     */
 #define TEXGS_REC_TEST_FLOATS 8    /* per-Gaussian TEST record (32 B): what the per-block culls and the alpha test read  */
 #define TEXGS_REC_SHADE_FLOATS 20  /* per-Gaussian SHADING record (80 B): fetched only for Gaussians that survive a cull (one record per
@@ -74,12 +74,14 @@ typedef struct TexGSInputs {
                                   (a selection: no gradient flows through it)                                           */
 } TexGSInputs;
 
-/* Per-Gaussian state written by texgs_preprocess_forward (K1) and texgs_read_num_rendered (K2). */
+/* Per-Gaussian state written by texgs_preprocess_forward (K1) and K2 (texgs_num_rendered_begin with sort_first, or
+ * texgs_depth_sort_scan). */
 typedef struct TexGSGeom {
     float*    rec_test;        /* f32[N,8]:  xy(2) conic(-a/2,-b,-c/2) opacity rcull thr -- read for EVERY (8x8 block, instance) pair */
     float*    rec_shade;       /* f32[N,20]: g(2) G(6) | phi(3) viewdep(3) | depth normal(3) xy(2) -- read only for instances
                                   that can reach alpha >= 1/255 somewhere in the block (about a third of them); the last two
-                                  words repeat the test record's xy (v15) so that K7's per-item gather needs one record    */
+                                  words repeat the test record's xy (v15, for the item-stream K7 removed in v17) and are
+                                  no longer read                                                                       */
     float*    depth;           /* f32[N] view-space z = the depth sort key (its bit pattern); 0xFFFFFFFF for culled Gaussians */
     int32_t*  radii;           /* i32[N] screen radius in px; 0 = culled (operator output `radii`)     */
     uint32_t* rect;            /* u32[N,2]: (minx | miny<<16), (maxx | maxy<<16) tile rectangle        */
@@ -135,29 +137,8 @@ typedef struct TexGSImage {
                                   grouping).  Footprints whose entry belongs to another bin (~2 %) are counted in the second half
                                   of tex_bin_count and appended through TexGSGrads.tex_bin_cursor.  No initialisation; written
                                   for every block.                                                                       */
-    /* K6 -> K7 ITEM STREAM (v15), all NULL / 0 or all set.  Set = "a backward that wants per-Gaussian gradients will follow": K6
-       appends, per 8x8 pixel block and in blend order (front to back), one 12-byte item {T before the pair, alpha_raw = opacity *
-       exp(power), Gaussian id << 6 | pixel lane} for every CONTRIBUTING (pixel, Gaussian) pair -- what the lineage's backward
-       recomputes per pair by replaying the tile list -- and K7 walks the block's items back to front instead of
-       re-testing the survivor lists: no test loop, no transmittance recurrence (T /= 1 - alpha), decisions identical by
-       construction.  Pages of TEXGS_ITEM_PAGE items (three planes of TEXGS_ITEM_PAGE words: T, alpha_raw, key) are taken from
-       item_sub_pools sub-pools of the buffer with one returning atomic per page; a block's pages are chained backwards through
-       item_link.  A buffer that is too small is not an error: K6 raises item_ctl[TEXGS_ITEM_CTL_FLAG], the stream kernel does
-       nothing and the survivor-replay kernel (the hand-off above, always written) runs instead; the cursors keep counting, so
-       max(item_ctl[16 * s]) * item_sub_pools is what the view needed (the caller sizes the next buffer from it). */
-    uint32_t* item_pages;      /* u32[item_page_cap * 3 * TEXGS_ITEM_PAGE]; no initialisation                                     */
-    uint32_t* item_link;       /* u32[item_page_cap]: the block's previous page (0xFFFFFFFF: none); no initialisation              */
-    uint32_t* item_tail;       /* u32[4 * T * 2]: per block {last page, items}; written for every block                            */
-    uint32_t* item_ctl;        /* u32[TEXGS_ITEM_CTL_WORDS]: sub-pool cursors (one per 64-byte line) + the overflow flag; zero-filled
-                                  by the library before K6                                                                         */
-    uint32_t  item_page_cap;   /* pages item_pages / item_link hold; sub-pool s owns pages [s * cap / pools, (s + 1) * cap / pools) */
-    uint32_t  item_sub_pools;  /* power of two, 1..TEXGS_ITEM_MAX_POOLS (one hot atomic word serialises at ~13 ns per request)    */
 } TexGSImage;
 #define TEXGS_RESV_WORDS 192
-#define TEXGS_ITEM_PAGE 256
-#define TEXGS_ITEM_MAX_POOLS 64
-#define TEXGS_ITEM_CTL_FLAG (16 * TEXGS_ITEM_MAX_POOLS)
-#define TEXGS_ITEM_CTL_WORDS (16 * TEXGS_ITEM_MAX_POOLS + 16)
 
 #define TEXGS_ACC_MEANS3D 1
 #define TEXGS_ACC_MEANS2D 2
@@ -238,25 +219,19 @@ size_t texgs_tex_bin_count(int32_t tex_res);
  * D = sum of tiles_touched (device word).  Replaces the first half of _C.rasterize_gaussians. */
 int texgs_preprocess_forward(const TexGSFrame* frame, const TexGSInputs* in, TexGSGeom* geom, void* stream);
 
-/* The one device->host sync of the forward (the lineage has the same one): starts the asynchronous readback of D,
- * launches K2 -- the sort of the N Gaussians by (depth bits, index) and the exclusive scan of tiles_touched in
- * that order, neither of which depends on D -- and only then waits for D, so the device is busy during the sync. */
-int texgs_read_num_rendered(const TexGSGeom* geom, int32_t num_gaussians, uint32_t* host_out, void* stream);
-
-/* The same readback, also returning K1's 64-bit GEOMETRY FINGERPRINT: a hash of everything the tile binning (K2-K5), K6's
- * survivor lists and its per-bin footprint counts are functions of (depth bits, tile rect, test record and the UV-Taylor part of
- * the shading record of every Gaussian).  Two forwards with equal fingerprints, image size and texture resolution have identical
- * TexGSBinning contents, survivor lists and tex_bin_count: the second may run texgs_render_forward on the first one's buffers
- * (the reference renders every training view twice, models/texture_gaussian3d.py:318 and :375-389 -- same camera, same
- * Gaussians, sh_degree 0 the second time).  Equality of a 64-bit hash, i.e. a 2^-64 chance of a false match per comparison.
- * sort_first != 0: launch K2 before waiting (as texgs_read_num_rendered does); 0: only wait -- the caller expects to re-use
- * existing lists and calls texgs_depth_sort_scan itself if the fingerprint turns out different. */
-int texgs_read_num_rendered2(const TexGSGeom* geom, int32_t num_gaussians, uint32_t* host_out, uint64_t* fingerprint_out,
-                             int32_t sort_first, void* stream);
-/* The same readback in two steps (v15), for a caller that issues K1 of a later view early so that no forward ever waits for its own
- * K1: texgs_num_rendered_begin copies K1's partial sums into the caller's PINNED host buffer (>= texgs_num_rendered_words(N) words)
- * asynchronously on `stream` and, with sort_first, launches K2; the caller records an event behind it.  texgs_num_rendered_reduce --
- * host only, after that event completed -- returns D and the geometry fingerprint. */
+/* The one device->host sync of the forward (the lineage has the same one), in two steps (v15) so that a caller can issue K1 of a
+ * later view early and no forward ever waits for its own K1: texgs_num_rendered_begin copies K1's partial sums into the caller's
+ * PINNED host buffer (>= texgs_num_rendered_words(N) words) asynchronously on `stream` and, with sort_first != 0, launches K2 --
+ * the sort of the N Gaussians by (depth bits, index) and the exclusive scan of tiles_touched in that order, neither of which
+ * depends on D -- so that the device is busy during the sync; the caller records an event behind it.  sort_first == 0: the
+ * caller expects to re-use existing lists and calls texgs_depth_sort_scan itself if the fingerprint turns out different.
+ * texgs_num_rendered_reduce -- host only, after that event completed -- returns D and K1's 64-bit GEOMETRY FINGERPRINT: a hash
+ * of everything the tile binning (K2-K5), K6's survivor lists and its per-bin footprint counts are functions of (depth bits,
+ * tile rect, test record and the UV-Taylor part of the shading record of every Gaussian).  Two forwards with equal
+ * fingerprints, image size and texture resolution have identical TexGSBinning contents, survivor lists and tex_bin_count: the
+ * second may run texgs_render_forward on the first one's buffers (the reference renders every training view twice,
+ * models/texture_gaussian3d.py:318 and :375-389 -- same camera, same Gaussians, sh_degree 0 the second time).  Equality of a
+ * 64-bit hash, i.e. a 2^-64 chance of a false match per comparison. */
 size_t texgs_num_rendered_words(int32_t num_gaussians);
 int texgs_num_rendered_begin(const TexGSGeom* geom, int32_t num_gaussians, uint32_t* host_pinned, size_t host_words, int32_t sort_first,
                              void* stream);
@@ -269,15 +244,6 @@ int texgs_depth_sort_scan(TexGSGeom* geom, int32_t num_gaussians, void* stream);
  * launch order, K6 16x16-tile alpha-blend with cubemap fetch.  Second half of _C.rasterize_gaussians. */
 int texgs_bin_sort_render_forward(const TexGSFrame* frame, const TexGSInputs* in, const TexGSGeom* geom,
                                   TexGSBinning* bin, TexGSImage* img, void* stream);
-
-/* Whole forward in one call: texgs_preprocess_forward, the num_rendered readback, and -- when D fits `capacity`
- * (the element count the caller sized keys/vals/point_list for; sort_temp_bytes >= texgs_sort_temp_bytes(capacity, T))
- * -- texgs_bin_sort_render_forward, with no host work between the sync and the next launches.  Returns
- * TEXGS_ERR_CAPACITY with *num_rendered_out = D when the buffers are too small: the caller grows them, sets
- * bin->num_rendered = D and calls texgs_bin_sort_render_forward itself. */
-#define TEXGS_ERR_CAPACITY 1000
-int texgs_forward(const TexGSFrame* frame, const TexGSInputs* in, TexGSGeom* geom, TexGSBinning* bin, uint32_t capacity,
-                  TexGSImage* img, uint32_t* num_rendered_out, void* stream);
 
 /* K6 alone on existing binning (re-render with a different texture / sh_degree-independent state). */
 int texgs_render_forward(const TexGSFrame* frame, const TexGSInputs* in, const TexGSGeom* geom,

@@ -1,6 +1,6 @@
 #!/bin/bash
 # usage (GPU box): scripts/ab_env.sh "VAR=1 VAR2=x" "VAR=0" ...   -- C3 bench per environment setting: serial kernel table and
-# pipelined views/s (e.g. "TEXGS_ITEMS=1" "TEXGS_ITEMS=0", or "TEXGS_LIB=$PWD/texture-gs_amd/libtexgs_x.so")
+# pipelined views/s (e.g. "TEXGS_LIB=$PWD/texture-gs_amd/libtexgs_x.so")
 R=$(cd "$(dirname "$0")/.." && pwd)
 O=${TEXGS_OUT:-$R/out}
 cd "$R"

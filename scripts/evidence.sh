@@ -33,7 +33,6 @@ TEXGS_UV_PRECISION=fp32 timeout 300 python bench.py --leg iteration --steps 10 -
 # the C3 geometry with a 302 MB texture (past the 256 MB Infinity Cache), serial and pipelined, beside R = 1024
 timeout 300 python bench.py --full --tex-res 2048 --no-cpu-baseline --no-extra-legs > $O/bench_c3_R2048.json 2> $O/bench_c3_R2048.err
 timeout 300 python bench.py --full --tex-res 2048 --streams 1 --no-cpu-baseline --no-extra-legs > $O/bench_c3_R2048_serial.json 2> $O/bench_c3_R2048_serial.err
-TEXGS_ITEMS=1 timeout 300 python bench.py --full --no-cpu-baseline --no-extra-legs > $O/bench_c3_items.json 2> $O/bench_c3_items.err
 echo "[bench $(( $(date +%s) - T0 )) s]"
 bash scripts/prof_ref_pattern.sh > $O/ref_pattern_profile.txt 2>&1
 echo "[ref pattern $(( $(date +%s) - T0 )) s]"
@@ -48,7 +47,7 @@ du -sh $O | tail -1
 python - <<'PY'
 import json, os
 O = os.environ["TEXGS_OUT"]
-for n in ("c3", "c3_again", "c3_noprefetch", "c3_serial", "c3_s4", "c2", "c5", "c3_diff_gauss", "c3_rccl1", "c3_R2048", "c3_R2048_serial", "c3_items"):
+for n in ("c3", "c3_again", "c3_noprefetch", "c3_serial", "c3_s4", "c2", "c5", "c3_diff_gauss", "c3_rccl1", "c3_R2048", "c3_R2048_serial"):
     try:
         j = json.loads([l for l in open(f"{O}/bench_{n}.json").read().splitlines() if l.startswith("{")][-1])
         print(n, j["value"], j.get("value_long"), j["ms_per_step_percentiles"]["median"], {k: round(v["avg_us"]) for k, v in j["kernels"].items()},

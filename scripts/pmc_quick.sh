@@ -13,7 +13,7 @@ env $ENVS rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $OUT/p3 -o p3 --output-fo
 env $ENVS rocprofv3 --pmc WRITE_SIZE TCC_HIT_sum TCC_MISS_sum --kernel-trace -d $OUT/p4 -o p4 --output-format csv -- $B > /dev/null 2>&1
 python - <<PY | tee $OUT/summary.txt
 import csv, glob, collections
-names = ("k_render_fwd", "k_render_bwd_stream", "k_render_bwd", "k_texgrad_reduce", "k_preprocess_bwd")
+names = ("k_render_fwd", "k_render_bwd", "k_texgrad_reduce", "k_preprocess_bwd")
 def short(n):
     for k in names:
         if k + "<" in n or k + "I" in n or n.startswith(k + "(") or (k in n and not any(k2 != k and k in k2 and k2 in n for k2 in names)): return k

@@ -19,10 +19,11 @@ def declared_functions():
     return sorted(set(re.findall(r"\b(texgs_[a-z_0-9]+)\s*\(", src)))
 
 
-def test_header_declares_expected_entry_points():
+def test_header_declares_the_entry_points_the_host_uses():
     names = declared_functions()
-    for n in ["texgs_preprocess_forward", "texgs_read_num_rendered", "texgs_bin_sort_render_forward",
-              "texgs_render_forward", "texgs_backward", "texgs_mark_visible", "texgs_abi_version", "texgs_last_error"]:
+    for n in ["texgs_preprocess_forward", "texgs_num_rendered_begin", "texgs_num_rendered_reduce", "texgs_depth_sort_scan",
+              "texgs_bin_sort_render_forward", "texgs_render_forward", "texgs_backward", "texgs_backward_render",
+              "texgs_backward_preprocess", "texgs_mark_visible", "texgs_abi_version", "texgs_last_error"]:
         assert n in names
 
 

@@ -471,7 +471,7 @@ def test_mark_visible_and_capacity_regrow(lib_built):
     assert torch.equal(vis, exp)
     outs_a, s_a = Hh.hip_debug_state(scene, cam, deg, bg)
     key = (dev.index, scene.means3D.shape[0], cam.image_height, cam.image_width)
-    RZ._CAPACITY_HINT[key] = 16                      # force TEXGS_ERR_CAPACITY -> grow -> second half
+    RZ._CAPACITY_HINT[key] = 16                      # force D > capacity -> grow -> second half
     outs_b, s_b = Hh.hip_debug_state(scene, cam, deg, bg)
     assert s_b.D == s_a.D and RZ._CAPACITY_HINT[key] >= s_a.D
     for x, y in zip(outs_a[:4], outs_b[:4]):

@@ -31,7 +31,7 @@ UNITS = {
     "abi.hip": [],
 }
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "wave_ops.h"), os.path.join(CSRC, "render_bwd_body.h"),
-           os.path.join(CSRC, "render_bwd_stream.h"), os.path.join(ROOT, "include", "texgs.h")]
+           os.path.join(ROOT, "include", "texgs.h")]
 
 
 def build_id():

@@ -121,58 +121,11 @@ static int depth_sort_scan(const TexGSFrame* frame, TexGSGeom* geom, hipStream_t
     return check(frame, s, "depth sort / scan");
 }
 
-namespace {
-struct Readback { uint32_t* host = nullptr; size_t words = 0; hipEvent_t ev = nullptr; };
-constexpr int RB_MAX_DEVICES = 64;
-thread_local Readback g_rb_dev[RB_MAX_DEVICES];   // one pinned word + event per (host thread, device): HIP events belong to the
-                                                  // device that was current when they were created
-}
-
-// D = sum of tiles_touched and the geometry fingerprint (K1 leaves per-workgroup partial sums of both): asynchronous copy into
-// pinned memory; with sort_first, K2 -- depth sort + scan, which WRITE geom->offsets and geom->scan_temp -- is launched before
-// the host waits, so the device stays busy during the one unavoidable device->host sync.
-int texgs_read_num_rendered2(const TexGSGeom* geom, int32_t num_gaussians, uint32_t* host_out, uint64_t* fingerprint_out,
-                             int32_t sort_first, void* stream) {
-    if (!geom || !host_out) return fail_msg("NULL argument");
-    *host_out = 0;
-    if (fingerprint_out) *fingerprint_out = 0;
-    if (num_gaussians <= 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= RB_MAX_DEVICES) return fail_msg("hipGetDevice failed");
-    Readback& g_rb = g_rb_dev[dev];
-    // K1 left five words per workgroup (three partial sums + the depth-key range, which only the device-side sort reads; no atomics,
-    // nothing to zero-fill): copy the three sums (3 * nblk words), add them up here
-    const size_t nblk = ((size_t)num_gaussians + TG_BLOCK - 1) / TG_BLOCK, nw = 3 * nblk;
-    if (g_rb.words < nw) {
-        if (g_rb.host) (void)hipHostFree(g_rb.host);
-        g_rb.host = nullptr;
-        g_rb.words = nw < 4096 ? 4096 : nw * 2;
-        if (hipHostMalloc((void**)&g_rb.host, g_rb.words * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess) { g_rb.words = 0; return fail_msg("hipHostMalloc failed"); }
-    }
-    if (!g_rb.ev && hipEventCreateWithFlags(&g_rb.ev, hipEventDisableTiming) != hipSuccess) return fail_msg("hipEventCreate failed");
-    hipError_t e = hipMemcpyAsync(g_rb.host, bin_block_sums_ptr(geom, num_gaussians), nw * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
-    if (e != hipSuccess) return fail("num_rendered readback", e);
-    e = hipEventRecord(g_rb.ev, s);
-    if (e != hipSuccess) return fail("num_rendered event", e);
-    if (sort_first) {
-        TexGSFrame f0; memset(&f0, 0, sizeof(f0)); f0.num_gaussians = num_gaussians;
-        if (int r = depth_sort_scan(&f0, const_cast<TexGSGeom*>(geom), s)) return r;
-    }
-    e = hipEventSynchronize(g_rb.ev);
-    if (e != hipSuccess) return fail("num_rendered sync", e);
-    unsigned long long total = 0ull;
-    uint32_t fa = 0u, fb = 0u;
-    for (size_t k = 0; k < nblk; ++k) { total += g_rb.host[k]; fa += g_rb.host[nblk + k]; fb += g_rb.host[2 * nblk + k]; }
-    if (total > 0xFFFFFFFFull) return fail_msg("num_rendered exceeds 2^32 - 1 instances");
-    *host_out = (uint32_t)total;
-    if (fingerprint_out) *fingerprint_out = ((uint64_t)fb << 32) | (uint64_t)fa;
-    return 0;
-}
-
-// The same readback in two steps, for a caller that issues K1 of a LATER view early (texgs.rasterizer forward prefetch): `begin` copies
-// K1's per-workgroup partial sums into the caller's PINNED host buffer asynchronously (and launches K2 with sort_first), the caller
-// records an event of its own behind it and goes on; `reduce` -- host only, after that event has completed -- adds them up.
+// D = sum of tiles_touched and the geometry fingerprint, read back in two steps so that a caller can issue K1 of a LATER view early
+// (texgs.rasterizer forward prefetch): `begin` copies K1's per-workgroup partial sums (three per workgroup; no atomics, nothing to
+// zero-fill) into the caller's PINNED host buffer asynchronously and, with sort_first, launches K2 -- depth sort + scan, which WRITE
+// geom->offsets and geom->scan_temp -- so the device stays busy during the sync; the caller records an event of its own behind it and
+// goes on; `reduce` -- host only, after that event has completed -- adds them up.
 size_t texgs_num_rendered_words(int32_t num_gaussians) {
     return num_gaussians <= 0 ? 0 : 3 * (((size_t)num_gaussians + TG_BLOCK - 1) / TG_BLOCK);
 }
@@ -206,10 +159,6 @@ int texgs_num_rendered_reduce(const uint32_t* host_pinned, int32_t num_gaussians
     return 0;
 }
 
-int texgs_read_num_rendered(const TexGSGeom* geom, int32_t num_gaussians, uint32_t* host_out, void* stream) {
-    return texgs_read_num_rendered2(geom, num_gaussians, host_out, nullptr, 1, stream);
-}
-
 int texgs_depth_sort_scan(TexGSGeom* geom, int32_t num_gaussians, void* stream) {
     if (!geom) return fail_msg("NULL argument");
     TexGSFrame f0; memset(&f0, 0, sizeof(f0)); f0.num_gaussians = num_gaussians;
@@ -225,18 +174,6 @@ static int render_forward_impl(const TexGSFrame* frame, const TexGSInputs* in, c
     if (img->tex_bin_count && in->texture && !counters_zeroed) {       // K6 counts the texture-gradient footprints per bin into it
         hipError_t e = hipMemsetAsync(img->tex_bin_count, 0, sizeof(uint32_t) * 2 * tex_bin_count(c.R), s);
         if (e != hipSuccess) return fail("tex_bin_count memset", e);
-    }
-    if (img->item_pages || img->item_link || img->item_tail || img->item_ctl) {       // the K6 -> K7 item stream: all or nothing
-        if (!img->item_pages || !img->item_link || !img->item_tail || !img->item_ctl)
-            return fail_msg("TexGSImage.item_pages / item_link / item_tail / item_ctl must be all NULL or all set");
-        if (!img->survivors) return fail_msg("the item stream needs the survivor hand-off beside it (its fallback)");
-        const uint32_t np = img->item_sub_pools;
-        if (np == 0u || np > TEXGS_ITEM_MAX_POOLS || (np & (np - 1u)) != 0u) return fail_msg("item_sub_pools must be a power of two in [1, 64]");
-        if (img->item_page_cap / np < 2u) return fail_msg("item_page_cap must hold at least two pages per sub-pool");
-        if (!counters_zeroed) {
-            hipError_t e = hipMemsetAsync(img->item_ctl, 0, sizeof(uint32_t) * TEXGS_ITEM_CTL_WORDS, s);
-            if (e != hipSuccess) return fail("item_ctl memset", e);
-        }
     }
     { ProfScope p(TEXGS_K_RENDER_FWD, s); launch_render_fwd(c, frame, in, geom, bin, img, s); }
     return check(frame, s, "render_fwd");
@@ -263,23 +200,9 @@ int texgs_bin_sort_render_forward(const TexGSFrame* frame, const TexGSInputs* in
     }
     // (the one-workgroup tile-order kernel also zero-fills the per-bin footprint counters K6 adds into)
     { ProfScope p(TEXGS_K_RANGES, s);
-      launch_ranges(c, bin, img->tex_bin_count, img->tex_bin_count ? 2 * (int)tex_bin_count(c.R) : 0,
-                    img->item_ctl, img->item_ctl ? TEXGS_ITEM_CTL_WORDS : 0, s); }
+      launch_ranges(c, bin, img->tex_bin_count, img->tex_bin_count ? 2 * (int)tex_bin_count(c.R) : 0, s); }
     if (int r = check(frame, s, "tile_ranges")) return r;
     return render_forward_impl(frame, in, geom, bin, img, stream, true);
-}
-
-int texgs_forward(const TexGSFrame* frame, const TexGSInputs* in, TexGSGeom* geom, TexGSBinning* bin, uint32_t capacity,
-                  TexGSImage* img, uint32_t* num_rendered_out, void* stream) {
-    if (!num_rendered_out || !bin) return fail_msg("NULL argument");
-    if (int r = texgs_preprocess_forward(frame, in, geom, stream)) return r;
-    if (int r = texgs_read_num_rendered(geom, frame->num_gaussians, num_rendered_out, stream)) return r;
-    bin->num_rendered = *num_rendered_out;
-    if (*num_rendered_out > capacity) {
-        snprintf(g_err, sizeof(g_err), "num_rendered %u exceeds binning capacity %u", *num_rendered_out, capacity);
-        return TEXGS_ERR_CAPACITY;
-    }
-    return texgs_bin_sort_render_forward(frame, in, geom, bin, img, stream);
 }
 
 int texgs_backward_render(const TexGSFrame* frame, const TexGSInputs* in, const TexGSGeom* geom,

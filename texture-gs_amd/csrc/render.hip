@@ -153,20 +153,7 @@ struct PixArgs {
     uint16_t* surv_qm;       // bit q: the survivor can reach quadrant q
     uint32_t* surv_cnt;      // [4 * tiles] survivors written per block
     uint32_t* resv;          // [4 * tiles][3][64] per-block reservation table {bin | offset inside the bin's list | count} (NULL: no binned texture gradient)
-    // K6 -> K7 ITEM STREAM (texgs.h v15; item_pages NULL: off): one {T, alpha_raw, Gaussian id << 6 | pixel lane} per contributing pair
-    uint32_t* item_pages;    // [cap][3][TG_PAGE]
-    uint32_t* item_link;     // [cap] previous page of the same block
-    uint32_t* item_tail;     // [4 * tiles][2] {last page, items}
-    uint32_t* item_ctl;      // sub-pool cursors (every 16th word) + overflow flag
-    uint32_t  item_sub_cap;  // pages per sub-pool
-    uint32_t  item_sub_mask; // sub-pools - 1
-    const uint32_t* run_if;  // the survivor-replay K7 only: do nothing unless this word is non-zero (NULL: always run)
 };
-#define TG_PAGE TEXGS_ITEM_PAGE
-#define TG_PAGE_SHIFT 8
-static_assert((1 << TG_PAGE_SHIFT) == TG_PAGE, "page size");
-#define TG_NOPAGE 0xFFFFFFFFu
-#define TG_PAGE_UNSET 0xFFFFFFFEu
 
 // workgroup (= one wave) -> (tile, 8x8 block).  Tiles are launched longest-list-first (tile_order).  The four blocks of a
 // tile get ids that are equal mod 8, so they run on the same XCD (workgroup b is observed on XCD b % 8: speed only) and
@@ -316,25 +303,6 @@ k_render_fwd(PixArgs a, float* __restrict__ out_color, float* __restrict__ out_d
     // The dense phase is software-pipelined by one batch: drain(n) first FINISHES the previous batch (its 4 taps were
     // loaded a whole batch interval ago: colour, Q32.32 accumulate), then STARTS the new one (queue pop, record fields, UV
     // Taylor step, cubemap address, tap loads issued) and returns without waiting for them.
-    // K6 -> K7 item stream (see PixArgs): pages from this block's sub-pool, one returning atomic per page, issued a page ahead
-    const bool streaming = a.item_pages != nullptr;
-    const uint32_t sub = (uint32_t)blockIdx.x & a.item_sub_mask;
-    uint32_t cur_page = TG_PAGE_UNSET, prev_page = TG_NOPAGE;      // wave-uniform
-    uint32_t pend_v = 0u;                      // lane 0: the pending allocation's result
-    int nitems = 0;
-    uint32_t cid = 0u;                         // lane = survivor of the current chunk: its Gaussian id
-    auto alloc_issue = [&]() { if (lane == 0) pend_v = atomicAdd(a.item_ctl + 16u * sub, 1u); };
-    auto alloc_take = [&](uint32_t prev) -> uint32_t {      // the pending allocation: its page (chained behind `prev`), or TG_NOPAGE
-        const uint32_t local = (uint32_t)__builtin_amdgcn_readfirstlane((int)pend_v);
-        if (local < a.item_sub_cap) {
-            const uint32_t page = sub * a.item_sub_cap + local;
-            if (lane == 0) a.item_link[page] = prev;
-            return page;
-        }
-        if (lane == 0) a.item_ctl[TEXGS_ITEM_CTL_FLAG] = 1u;     // the buffer is too small: the survivor-replay K7 runs instead
-        return TG_NOPAGE;
-    };
-    if (streaming && todo > 0) alloc_issue();
     int pn = 0;                                // lanes of the batch in flight (wave-uniform)
     int p_pl = 0;
     float p_w = 0.f, p_fx = 0.f, p_fy = 0.f, p_vd0 = 0.f, p_vd1 = 0.f, p_vd2 = 0.f;
@@ -366,29 +334,14 @@ k_render_fwd(PixArgs a, float* __restrict__ out_color, float* __restrict__ out_d
         const int jj_ = KEY_J(e_.y);
         const float4 f_ = L.p.F[jj_];
         const float2 g2 = L.p.G[jj_];
-        // The queue carries T (what K7 needs), not w: alpha_raw is evaluated again here from the same planes with the same
-        // explicitly ordered operations as in the test loop -- bit-identical -- and w = min(0.99, alpha_raw) * T as there.
+        // The queue carries T (what the item stream of ABI v15-v16 stored), not w: alpha_raw is evaluated again here from the same
+        // planes with the same explicitly ordered operations as in the test loop -- bit-identical -- and w = min(0.99, alpha_raw) * T as there.
         const float4 a4_ = L.p.A[jj_];
         const float2 b2_ = *reinterpret_cast<const float2*>(&L.p.B[jj_]);
         const float ipx_ = (float)(wave_px + KEY_OX(e_.y)), ipy_ = (float)(wave_py + KEY_OY(e_.y));
         const float araw_ = gauss_alpha_raw(b2_.y, gauss_power(a4_.z, a4_.w, b2_.x, a4_.x - ipx_, a4_.y - ipy_));
         const float T_ = __uint_as_float(e_.x);
         const float w_ = fminf(TG_ALPHA_MAX, araw_) * T_;
-        if (streaming) {
-            if (cur_page == TG_PAGE_UNSET) { cur_page = alloc_take(TG_NOPAGE); alloc_issue(); }
-            const bool cross = ((nitems + n_) >> TG_PAGE_SHIFT) != (nitems >> TG_PAGE_SHIFT);
-            uint32_t nxt = TG_NOPAGE;
-            if (cross) { nxt = alloc_take(cur_page); alloc_issue(); }
-            const uint32_t v = (uint32_t)nitems + (uint32_t)lane;
-            const uint32_t page = ((v >> TG_PAGE_SHIFT) == ((uint32_t)nitems >> TG_PAGE_SHIFT)) ? cur_page : nxt;
-            const uint32_t gid = (uint32_t)__builtin_amdgcn_ds_bpermute(jj_ << 2, (int)cid);
-            if (lane < n_ && page != TG_NOPAGE) {
-                uint32_t* __restrict__ pb = a.item_pages + (size_t)page * (3 * TG_PAGE) + (v & (TG_PAGE - 1));
-                nt_store(pb, e_.x); nt_store(pb + TG_PAGE, __float_as_uint(araw_)); nt_store(pb + 2 * TG_PAGE, (gid << 6) | (uint32_t)KEY_PL(e_.y));
-            }
-            if (cross) { prev_page = cur_page; cur_page = nxt; }
-            nitems += n_;
-        }
         if constexpr (TAPS) {
             const float2 xy = make_float2(a4_.x, a4_.y);
             const float4 d_ = L.p.D[jj_], e4 = L.p.E[jj_];
@@ -476,7 +429,6 @@ k_render_fwd(PixArgs a, float* __restrict__ out_color, float* __restrict__ out_d
         }
         qh = (qh + take) & (TG_RING - 1); nq -= take;
         float4 T0, T1;
-        cid = id;
         load_chunk(a, L.p, lane, lane < take, id, pos, T0, T1);     // (every item of the previous chunk was started by a drain: its fields are in registers)
         reinterpret_cast<uint32_t*>(&L.list[0][0])[lane] = 0x40404040u;      // pad all four lists with TG_DUMMY
         __builtin_amdgcn_wave_barrier();
@@ -578,11 +530,6 @@ k_render_fwd(PixArgs a, float* __restrict__ out_color, float* __restrict__ out_d
         nt_store(rv + lane, b); nt_store(rv + TG_RESV + lane, off); nt_store(rv + 2 * TG_RESV + lane, n);
     }
     if (a.surv_cnt != nullptr && lane == 0) a.surv_cnt[4 * tile + wave] = (uint32_t)nsurv;
-    if (streaming && lane == 0) {
-        // the page that holds the block's LAST item (a stream that ends exactly on a page boundary has already moved on)
-        const uint32_t tailp = (nitems > 0 && (nitems & (TG_PAGE - 1)) == 0) ? prev_page : cur_page;
-        reinterpret_cast<uint2*>(a.item_tail)[4 * tile + wave] = make_uint2(tailp, (uint32_t)nitems);
-    }
     if (inside) {
         const int HW = a.W * a.H, pix = py * a.W + px;
         const double q = 1.0 / 4294967296.0;
@@ -710,19 +657,6 @@ namespace k7_lds {
 #undef K7_GATHER
 #undef K7_WAVES_PER_SIMD
 }  // namespace k7_lds
-// K7 over K6's item stream (texgs.h v15): the flavours with the per-Gaussian stages.  Same registers-per-wave target as k7_occ.
-#ifdef K7S_TRACE
-#ifndef K7_TRACE_BLOCKS
-#define K7_TRACE_BLOCKS 32768
-#endif
-__device__ unsigned long long k7s_trace[8 * K7_TRACE_BLOCKS];
-#endif
-#ifndef K7S_WAVES_PER_SIMD
-#define K7S_WAVES_PER_SIMD 4
-#endif
-namespace k7_stream {
-#include "render_bwd_stream.h"
-}  // namespace k7_stream
 
 // ------------------------------------------------------------------------------------------------ texture-gradient lists
 // Exclusive scan of K6's per-bin footprint counts -> list offsets (one workgroup; nbins = 6144 at R = 1024).  count[b] = the
@@ -898,15 +832,6 @@ inline PixArgs make_pix(const CamConst& c, const TexGSFrame* f, const TexGSInput
     a.surv_qm = hand ? img->surv_qmask : nullptr;
     a.surv_cnt = hand ? img->surv_count : nullptr;
     a.resv = img->tex_bin_resv;
-    const bool items = hand && img->item_pages != nullptr && img->item_link != nullptr && img->item_tail != nullptr &&
-                       img->item_ctl != nullptr && img->item_sub_pools != 0u;
-    a.item_pages = items ? img->item_pages : nullptr;
-    a.item_link = items ? img->item_link : nullptr;
-    a.item_tail = items ? img->item_tail : nullptr;
-    a.item_ctl = items ? img->item_ctl : nullptr;
-    a.item_sub_cap = items ? img->item_page_cap / img->item_sub_pools : 0u;
-    a.item_sub_mask = items ? img->item_sub_pools - 1u : 0u;
-    a.run_if = nullptr;
     return a;
 }
 
@@ -947,7 +872,7 @@ void launch_render_fwd(const CamConst& c, const TexGSFrame* f, const TexGSInputs
 // operator.
 void launch_render_bwd(const CamConst& c, const TexGSFrame* f, const TexGSInputs* in, const TexGSGeom* g,
                        const TexGSBinning* b, const TexGSImage* img, TexGSGrads* gr, hipStream_t s) {
-    const PixArgs a0 = make_pix(c, f, in, g, b, img);
+    const PixArgs a = make_pix(c, f, in, g, b, img);
     const TexBinArgs tb = make_bins(c, img, gr);
     const bool taps = in->texture != nullptr;
     const bool tex = taps && (gr->want & TEXGS_WANT_TEXTURE) && gr->dL_dtexture != nullptr;
@@ -956,19 +881,7 @@ void launch_render_bwd(const CamConst& c, const TexGSFrame* f, const TexGSInputs
     if (tex && tb.rec)      // list offsets + cursors from the counts the forward left (one small workgroup)
         hipLaunchKernelGGL(k_bin_offsets, dim3(1), dim3(1024), 0, s, (int)tex_bin_count(c.R), (const uint32_t*)img->tex_bin_count,
                            gr->tex_bin_base, gr->tex_bin_cursor, gr->tex_bin_base + tex_bin_count(c.R) + 1, tb.stats);
-    const dim3 grid(blend_grid(a0.num_tiles)), blk(64);
-    PixArgs a = a0;
-    if (geo && a.item_pages != nullptr) {
-        // the forward left its item stream: the dense kernel over it; the survivor-replay kernel behind it runs only if K6 ran out of
-        // pages (one word decides for the whole view; ~10^4 empty workgroups otherwise)
-#define K7S_LAUNCH(TEX, UVG, TAPS) hipLaunchKernelGGL((k7_stream::k_render_bwd_stream<TEX, UVG, TAPS>), grid, blk, 0, s, a, tb, img->final_T, \
-        gr->dL_dcolor, gr->dL_ddepth, gr->dL_dnorm, gr->dL_dalpha, gr->acc, gr->dL_dtexture)
-        if (!taps)      K7S_LAUNCH(false, false, false);
-        else if (tex)   K7S_LAUNCH(true, true, true);
-        else            K7S_LAUNCH(false, true, true);
-#undef K7S_LAUNCH
-        a.run_if = a.item_ctl + TEXGS_ITEM_CTL_FLAG;
-    }
+    const dim3 grid(blend_grid(a.num_tiles)), blk(64);
 #define K7_LAUNCH(NS, TEX, GEO, UVG, TAPS) hipLaunchKernelGGL((NS::k_render_bwd<TEX, GEO, UVG, TAPS>), grid, blk, 0, s, a, tb, img->final_T, \
         img->n_contrib, gr->dL_dcolor, gr->dL_ddepth, gr->dL_dnorm, gr->dL_dalpha, gr->acc, gr->dL_dtexture)
     if (!taps)            K7_LAUNCH(k7_occ, false, true, false, false);
@@ -988,11 +901,6 @@ void launch_texgrad_reduce(const CamConst& c, const TexGSImage* img, TexGSGrads*
     hipLaunchKernelGGL(k_texgrad_reduce, dim3((unsigned)tex_bin_count(c.R)), dim3(TB_THREADS), 0, s, c.R, tb, gr->dL_dtexture);
 }
 
-#ifdef K7S_TRACE
-extern "C" __attribute__((visibility("default"))) int texgs_debug_k7s_trace(void* host_dst) {
-    return (int)hipMemcpyFromSymbol(host_dst, HIP_SYMBOL(k7s_trace), sizeof(unsigned long long) * 8 * K7_TRACE_BLOCKS);
-}
-#endif
 #ifdef K7_TRACE
 extern "C" __attribute__((visibility("default"))) int texgs_debug_k7_trace(void* host_dst) {
     return (int)hipMemcpyFromSymbol(host_dst, HIP_SYMBOL(k7_trace), sizeof(unsigned long long) * 4 * K7_TRACE_BLOCKS);

@@ -35,7 +35,6 @@ k_render_bwd(PixArgs a, TexBinArgs tb, const float* __restrict__ final_T, const 
     const int lane = (int)threadIdx.x;
     int tile, wave;
     if (!wave_block(a, tile, wave)) return;
-    if (a.run_if != nullptr && *a.run_if == 0u) return;      // launched as the item-stream kernel's fallback, and K6 did not run out of pages
 #ifdef K7_TRACE
     const unsigned long long trace_t0 = wall_clock64();   // experiment builds only (scripts/k7_trace.py): when each block ran, and where
 #endif

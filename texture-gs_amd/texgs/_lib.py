@@ -6,17 +6,12 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TEXGS_LIB") or os.path.join(os.path.dirname(_HERE), "libtexgs.so")   # TEXGS_LIB: experiment builds only
 
-ABI_VERSION = 16
-ERR_CAPACITY = 1000
+ABI_VERSION = 17
 TILE = 16
 REC_TEST_FLOATS = 8
 REC_SHADE_FLOATS = 20
 TEXBIN_RECORD_FLOATS = 4        # 16-byte texture-gradient records (TexGSGrads.tex_bins)
 RESV_WORDS = 192         # per 8x8 pixel block: 64 reservation entries x {bin, offset, count} (TexGSImage.tex_bin_resv)
-ITEM_PAGE = 256          # items per page of the K6 -> K7 item stream (TexGSImage.item_pages: three planes of ITEM_PAGE words per page)
-ITEM_MAX_POOLS = 64
-ITEM_CTL_FLAG = 16 * ITEM_MAX_POOLS
-ITEM_CTL_WORDS = 16 * ITEM_MAX_POOLS + 16
 ACC_FLOATS = 32
 WANT_TEXTURE, WANT_GAUSSIANS, WANT_ALL = 1, 2, 3
 
@@ -48,9 +43,7 @@ class Binning(C.Structure):
 class Image(C.Structure):
     _fields_ = [("out_color", _fp), ("out_depth", _fp), ("out_norm", _fp), ("out_alpha", _fp),
                 ("final_T", _fp), ("n_contrib", _fp), ("tex_bin_count", _fp),
-                ("survivors", _fp), ("surv_qmask", _fp), ("surv_count", _fp), ("tex_bin_resv", _fp),
-                ("item_pages", _fp), ("item_link", _fp), ("item_tail", _fp), ("item_ctl", _fp),
-                ("item_page_cap", C.c_uint32), ("item_sub_pools", C.c_uint32)]
+                ("survivors", _fp), ("surv_qmask", _fp), ("surv_count", _fp), ("tex_bin_resv", _fp)]
 
 
 class Grads(C.Structure):
@@ -81,8 +74,8 @@ class UVNetGradStruct(C.Structure):
 
 
 EXPORTS = ["texgs_abi_version", "texgs_build_id", "texgs_last_error", "texgs_scan_temp_bytes", "texgs_sort_temp_bytes",
-           "texgs_preprocess_forward", "texgs_read_num_rendered", "texgs_read_num_rendered2", "texgs_num_rendered_words", "texgs_num_rendered_begin", "texgs_num_rendered_reduce", "texgs_depth_sort_scan", "texgs_bin_sort_render_forward",
-           "texgs_render_forward", "texgs_forward", "texgs_backward", "texgs_backward_render", "texgs_backward_preprocess",
+           "texgs_preprocess_forward", "texgs_num_rendered_words", "texgs_num_rendered_begin", "texgs_num_rendered_reduce", "texgs_depth_sort_scan", "texgs_bin_sort_render_forward",
+           "texgs_render_forward", "texgs_backward", "texgs_backward_render", "texgs_backward_preprocess",
            "texgs_rgb_alpha_loss", "texgs_mark_visible", "texgs_profile_enable", "texgs_tex_bin_count",
            "texgs_profile_read", "texgs_profile_select", "texgs_selftest_waveops", "texgs_geom_losses", "texgs_norm_from_depth", "texgs_uv_taylor", "texgs_uv_taylor_temp_bytes", "texgs_uv_pack", "texgs_uv_taylor_packed",
            "texgs_uv_pack_bf16x3", "texgs_uv_taylor_packed_bf16x3", "texgs_uv_backward", "texgs_uv_backward_mixed", "texgs_uv_backward_temp_bytes", "texgs_uv_pack_mixed", "texgs_uv_taylor_packed_mixed",
@@ -114,9 +107,6 @@ def load():
     lib.texgs_tex_bin_count.restype = C.c_size_t
     lib.texgs_tex_bin_count.argtypes = [C.c_int32]
     lib.texgs_preprocess_forward.argtypes = [P(Frame), P(Inputs), P(Geom), C.c_void_p]
-    lib.texgs_read_num_rendered.argtypes = [P(Geom), C.c_int32, P(C.c_uint32), C.c_void_p]
-    lib.texgs_read_num_rendered2.argtypes = [P(Geom), C.c_int32, P(C.c_uint32), P(C.c_uint64), C.c_int32, C.c_void_p]
-    lib.texgs_read_num_rendered2.restype = C.c_int
     lib.texgs_num_rendered_words.argtypes = [C.c_int32]
     lib.texgs_num_rendered_words.restype = C.c_size_t
     lib.texgs_num_rendered_begin.argtypes = [P(Geom), C.c_int32, C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p]
@@ -127,8 +117,6 @@ def load():
     lib.texgs_depth_sort_scan.restype = C.c_int
     lib.texgs_bin_sort_render_forward.argtypes = [P(Frame), P(Inputs), P(Geom), P(Binning), P(Image), C.c_void_p]
     lib.texgs_render_forward.argtypes = [P(Frame), P(Inputs), P(Geom), P(Binning), P(Image), C.c_void_p]
-    lib.texgs_forward.argtypes = [P(Frame), P(Inputs), P(Geom), P(Binning), C.c_uint32, P(Image), P(C.c_uint32), C.c_void_p]
-    lib.texgs_forward.restype = C.c_int
     lib.texgs_backward.argtypes = [P(Frame), P(Inputs), P(Geom), P(Binning), P(Image), P(Grads), C.c_void_p]
     lib.texgs_backward_render.argtypes = [P(Frame), P(Inputs), P(Geom), P(Binning), P(Image), P(Grads), C.c_void_p]
     lib.texgs_backward_preprocess.argtypes = [P(Frame), P(Inputs), P(Geom), P(Grads), C.c_void_p]
@@ -184,8 +172,8 @@ def load():
     lib.texgs_profile_select.restype = C.c_int
     lib.texgs_profile_read.argtypes = [P(C.c_float), P(C.c_uint32)]
     lib.texgs_profile_read.restype = C.c_int
-    for name in ("texgs_preprocess_forward", "texgs_read_num_rendered", "texgs_bin_sort_render_forward",
-                 "texgs_render_forward", "texgs_forward", "texgs_backward", "texgs_backward_render",
+    for name in ("texgs_preprocess_forward", "texgs_bin_sort_render_forward",
+                 "texgs_render_forward", "texgs_backward", "texgs_backward_render",
                  "texgs_backward_preprocess", "texgs_rgb_alpha_loss", "texgs_mark_visible"):
         getattr(lib, name).restype = C.c_int
     v = lib.texgs_abi_version()
