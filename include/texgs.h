@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define TEXGS_ABI_VERSION 17
+#define TEXGS_ABI_VERSION 18
 #define TEXGS_TILE 16          /* 16x16 pixel tiles, one 256-thread workgroup (4 wave64) per tile     */
 #define TEXGS_REC_TEST_FLOATS 8    /* per-Gaussian TEST record (32 B): what the per-block culls and the alpha test read  */
 #define TEXGS_REC_SHADE_FLOATS 20  /* per-Gaussian SHADING record (80 B): fetched only for Gaussians that survive a cull (one record per
@@ -399,6 +399,22 @@ int texgs_hashgrid_backward(const TexGSHashGrid* grid, const float* params, cons
  * lowest j among equal distances.  A point with no finite distance gets d2 = NaN, idx = 0.  temp: texgs_chamfer_nn_temp_bytes(P). */
 size_t texgs_chamfer_nn_temp_bytes(int32_t P);
 int texgs_chamfer_nn(const float* a, int32_t P, const float* b, int32_t Q, float* d2, int32_t* idx, void* temp, void* stream);
+
+/* ---- point clouds between the stages (v18; csrc/points.hip) -------------------------------------------------------------------
+ * Both take xyz f32[n, 3] (finite values: the caller checks) and use, for points a and b,
+ *   dx = a.x - b.x; dy = a.y - b.y; dz = a.z - b.z; d2 = (dx*dx + dy*dy) + dz*dz, every operation rounded to fp32 (no FMA).
+ *
+ * mean_d2[i] = ((b0 + b1) + b2) / 3.0f, b0 <= b1 <= b2 the three smallest d2(xyz[i], xyz[j]) over j != i (excluded by index: a
+ * duplicate point contributes 0) -- simple_knn's distCUDA2 (models/gaussian3d.py:63).  n >= 4, else an error and no launch.
+ * temp: texgs_knn3_temp_bytes(n). */
+size_t texgs_knn3_temp_bytes(int32_t n);
+int texgs_knn3_mean_dist2(const float* xyz, int32_t n, float* mean_d2, void* temp, void* stream);
+/* Farthest-point sampling (pytorch3d.ops.sample_farthest_points, random_start_point=False; extract_pcd.py:18-20): idx[0] = start,
+ * m[j] = +inf; for t = 1 .. k-1: m[j] = min(m[j], d2(xyz[j], xyz[idx[t-1]])) for every j, idx[t] = argmax_j m[j], the LOWEST j on
+ * ties.  1 <= k <= n and 0 <= start < n, else an error and no launch.  k - 1 launches on `stream`, no host synchronisation.
+ * temp: texgs_fps_temp_bytes(n, k). */
+size_t texgs_fps_temp_bytes(int32_t n, int32_t k);
+int texgs_farthest_points(const float* xyz, int32_t n, int32_t k, int32_t start, int32_t* idx, void* temp, void* stream);
 
 /* Hardware self-test of the wave64 cross-lane primitives the backward's reductions use (csrc/wave_ops.h: DPP lane^4 /
  * lane^8 exchanges, permlane16/32 swaps, both transposing butterflies).  seed: f32[128] device; out: f32[576] device,

@@ -1,7 +1,8 @@
 """Build libtexgs.so (hipcc, gfx950 only) in-tree.  Usage: python texture-gs_amd/build.py [--force] [--verbose]
 
 Objects are rebuilt only when their sources are newer.  preprocess.hip is built with -ffp-contract=off (its
-fp32 operation order is part of the bit-exact key/rect/radius contract); the render kernels allow contraction
+fp32 operation order is part of the bit-exact key/rect/radius contract) and so is points.hip (its squared distance is
+compared bit for bit); the render kernels allow contraction
 and use hardware fp32 atomics (-munsafe-fp-atomics).
 """
 import os
@@ -28,6 +29,7 @@ UNITS = {
     "selftest.hip": [],
     "uvnet.hip": [],
     "uvmap.hip": ["-munsafe-fp-atomics"],
+    "points.hip": ["-ffp-contract=off"],      # its squared distance is a bit-exact contract: no fused multiply-add
     "abi.hip": [],
 }
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "wave_ops.h"), os.path.join(CSRC, "render_bwd_body.h"),

@@ -484,6 +484,26 @@ int texgs_chamfer_nn(const float* a, int32_t P, const float* b, int32_t Q, float
     return e == hipSuccess ? 0 : fail("chamfer_nn", e);
 }
 
+size_t texgs_knn3_temp_bytes(int32_t n) { return knn3_temp_bytes(n); }
+
+int texgs_knn3_mean_dist2(const float* xyz, int32_t n, float* mean_d2, void* temp, void* stream) {
+    if (n < 4) return fail_msg("n < 4: three nearest other points need at least four points");
+    if (!xyz || !mean_d2 || !temp) return fail_msg("NULL argument");
+    if (int r = launch_knn3_mean_dist2(xyz, n, mean_d2, temp, (hipStream_t)stream)) return fail("knn3_mean_dist2", (hipError_t)r);
+    return 0;
+}
+
+size_t texgs_fps_temp_bytes(int32_t n, int32_t k) { return fps_temp_bytes(n, k); }
+
+int texgs_farthest_points(const float* xyz, int32_t n, int32_t k, int32_t start, int32_t* idx, void* temp, void* stream) {
+    if (n < 1) return fail_msg("n < 1");
+    if (k < 1 || k > n) return fail_msg("k must be in [1, n]");
+    if (start < 0 || start >= n) return fail_msg("start must be in [0, n)");
+    if (!xyz || !idx || !temp) return fail_msg("NULL argument");
+    if (int r = launch_farthest_points(xyz, n, k, start, idx, temp, (hipStream_t)stream)) return fail("farthest_points", (hipError_t)r);
+    return 0;
+}
+
 int texgs_selftest_waveops(const float* seed128, float* out576, void* stream) {
     if (!seed128 || !out576) return fail_msg("NULL argument");
     launch_selftest_waveops(seed128, out576, (hipStream_t)stream);

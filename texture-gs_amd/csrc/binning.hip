@@ -916,6 +916,44 @@ int launch_sort(const CamConst& c, const TexGSGeom* g, TexGSBinning* b, hipStrea
     return (int)hipGetLastError();
 }
 
+// Stable LSD sort of n (u32 key, element index) pairs over the low `key_bits` bits (points.hip: Morton codes) with the same count /
+// scatter kernels, instantiated for 32-bit keys (MODE 0; the first pass takes val = element index).  temp: the passes' tables and
+// one ping-pong pair; the last pass lands in keys_out / vals_out.
+constexpr int PAIR_PASSES_MAX = 4;
+inline size_t pair_tables_bytes() {
+    return zero_header_bytes(PAIR_PASSES_MAX, 0) + align256(PAIR_PASSES_MAX * (size_t)RS_MAX_BLOCKS * 256 * 4);
+}
+size_t sort_pairs32_temp_bytes(uint32_t n) { return pair_tables_bytes() + 2 * align256((size_t)(n > 0 ? n : 1) * 4); }
+
+int launch_sort_pairs32(const uint32_t* keys_in, uint32_t n, int key_bits, uint32_t* keys_out, uint32_t* vals_out, void* temp, hipStream_t s) {
+    if (n == 0) return 0;
+    const int npass = (key_bits + 7) / 8;
+    if (key_bits < 1 || npass > PAIR_PASSES_MAX) return (int)hipErrorInvalidValue;
+    uint32_t* tbl = reinterpret_cast<uint32_t*>(temp);
+    uint32_t* tk = reinterpret_cast<uint32_t*>((char*)temp + pair_tables_bytes());
+    uint32_t* tv = reinterpret_cast<uint32_t*>((char*)tk + align256((size_t)n * 4));
+    if (hipError_t e = hipMemsetAsync(tbl, 0, zero_header_bytes(PAIR_PASSES_MAX, 0), s)) return (int)e;
+    uint32_t blocks, per;
+    pass_geometry(n, blocks, per);
+    const uint32_t* sk = keys_in;
+    const uint32_t* sv = nullptr;
+    int shift = 0, left = key_bits;
+    for (int pass = 0; pass < npass; ++pass) {
+        const int bits = (left + (npass - pass) - 1) / (npass - pass);
+        const RadixTables t = tables_at(tbl, pass, PAIR_PASSES_MAX, 0);
+        const uint32_t mask = (1u << bits) - 1u;
+        const bool to_out = ((npass - 1 - pass) & 1) == 0;             // the last pass writes the caller's arrays
+        uint32_t* dk = to_out ? keys_out : tk;
+        uint32_t* dv = to_out ? vals_out : tv;
+        hipLaunchKernelGGL(k_radix_count<uint32_t>, dim3(blocks), dim3(RS_THREADS), 0, s, sk, (const uint32_t*)nullptr, n, per, shift, mask, t);
+        hipLaunchKernelGGL((k_radix_scatter<uint32_t, 0>), dim3(blocks), dim3(RS_THREADS), 0, s, sk, sv, dk, dv, (const uint32_t*)nullptr, n,
+                           per, shift, mask, bits, t, (const uint32_t*)nullptr, (const uint32_t*)nullptr);
+        sk = dk; sv = dv;
+        shift += bits; left -= bits;
+    }
+    return (int)hipGetLastError();
+}
+
 void launch_ranges(const CamConst& c, TexGSBinning* b, uint32_t* zero_words, int num_zero_words, hipStream_t s) {
     const uint32_t T = (uint32_t)(c.tiles_x * c.tiles_y);
     if (b->num_rendered == 0) (void)hipMemsetAsync(b->ranges, 0, sizeof(uint32_t) * 2 * T, s);     // no K3 ran: every tile is empty

@@ -98,3 +98,9 @@ int launch_hashgrid_backward(const TexGSHashGrid* g, const float* params, const 
                              float* d_x, void* temp, hipStream_t s);
 size_t chamfer_nn_temp_bytes(int P);
 int launch_chamfer_nn(const float* a, int P, const float* b, int Q, float* d2, int32_t* idx, void* temp, hipStream_t s);
+size_t sort_pairs32_temp_bytes(uint32_t n);
+int launch_sort_pairs32(const uint32_t* keys_in, uint32_t n, int key_bits, uint32_t* keys_out, uint32_t* vals_out, void* temp, hipStream_t s);
+size_t knn3_temp_bytes(int n);
+int launch_knn3_mean_dist2(const float* xyz, int n, float* mean_d2, void* temp, hipStream_t s);
+size_t fps_temp_bytes(int n, int k);
+int launch_farthest_points(const float* xyz, int n, int k, int start, int32_t* idx, void* temp, hipStream_t s);

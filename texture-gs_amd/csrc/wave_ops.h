@@ -52,6 +52,25 @@ __device__ __forceinline__ int wave_max_i(int v) {
     return v;
 }
 
+__device__ __forceinline__ float wave_min_f(float v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v = fminf(v, __shfl_xor(v, m, 64));
+    return v;
+}
+__device__ __forceinline__ float wave_max_f(float v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v = fmaxf(v, __shfl_xor(v, m, 64));
+    return v;
+}
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        const unsigned long long o = __shfl_xor(v, m, 64);
+        v = o > v ? o : v;
+    }
+    return v;
+}
+
 // Transposing butterfly over NV (= 16 or 32) per-lane values: on return every lane l holds the sum over the 64 lanes
 // of v[l & (NV-1)].  Each halving step keeps one of a pair and sends the other to the partner lane, so the live
 // value count halves per step: 3*NV/2 + ... VALU instead of NV full reductions.

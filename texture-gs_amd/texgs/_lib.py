@@ -6,7 +6,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TEXGS_LIB") or os.path.join(os.path.dirname(_HERE), "libtexgs.so")   # TEXGS_LIB: experiment builds only
 
-ABI_VERSION = 17
+ABI_VERSION = 18
 TILE = 16
 REC_TEST_FLOATS = 8
 REC_SHADE_FLOATS = 20
@@ -80,7 +80,8 @@ EXPORTS = ["texgs_abi_version", "texgs_build_id", "texgs_last_error", "texgs_sca
            "texgs_profile_read", "texgs_profile_select", "texgs_selftest_waveops", "texgs_geom_losses", "texgs_norm_from_depth", "texgs_uv_taylor", "texgs_uv_taylor_temp_bytes", "texgs_uv_pack", "texgs_uv_taylor_packed",
            "texgs_uv_pack_bf16x3", "texgs_uv_taylor_packed_bf16x3", "texgs_uv_backward", "texgs_uv_backward_mixed", "texgs_uv_backward_temp_bytes", "texgs_uv_pack_mixed", "texgs_uv_taylor_packed_mixed",
            "texgs_hashgrid_levels", "texgs_hashgrid_forward", "texgs_hashgrid_backward_temp_bytes", "texgs_hashgrid_backward",
-           "texgs_chamfer_nn_temp_bytes", "texgs_chamfer_nn"]
+           "texgs_chamfer_nn_temp_bytes", "texgs_chamfer_nn",
+           "texgs_knn3_temp_bytes", "texgs_knn3_mean_dist2", "texgs_fps_temp_bytes", "texgs_farthest_points"]
 KERNEL_NAMES = ["preprocess_fwd", "scan", "duplicate", "sort", "ranges", "render_fwd", "render_bwd", "preprocess_bwd",
                 "texgrad_reduce"]
 
@@ -164,6 +165,14 @@ def load():
     lib.texgs_chamfer_nn_temp_bytes.restype = C.c_size_t
     lib.texgs_chamfer_nn.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.texgs_chamfer_nn.restype = C.c_int
+    lib.texgs_knn3_temp_bytes.argtypes = [C.c_int32]
+    lib.texgs_knn3_temp_bytes.restype = C.c_size_t
+    lib.texgs_knn3_mean_dist2.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.texgs_knn3_mean_dist2.restype = C.c_int
+    lib.texgs_fps_temp_bytes.argtypes = [C.c_int32, C.c_int32]
+    lib.texgs_fps_temp_bytes.restype = C.c_size_t
+    lib.texgs_farthest_points.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.texgs_farthest_points.restype = C.c_int
     lib.texgs_selftest_waveops.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     lib.texgs_selftest_waveops.restype = C.c_int
     lib.texgs_profile_enable.argtypes = [C.c_int]
