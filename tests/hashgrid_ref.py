@@ -14,6 +14,24 @@ import torch
 M32 = 0xFFFFFFFF
 PRIMES = (1, 2654435761, 805459861)
 SHIPPED = dict(n_levels=8, n_features=4, log2_hashmap_size=12, base_resolution=16.0, per_level_scale=1.447)
+# Grids off the shipped one (fields not named are SHIPPED's) and the row count of every level.  With the shipped grid every level has
+# 4096 rows, exactly the largest slab the backward accumulates in LDS (size * 16 B <= 64 KiB, csrc/uvmap.hip); these reach the
+# rest: levels on the global-atomic path, both launches in one call, dense levels that are no power of two (roundup8(res^3)),
+# L != 8, and a table so small that every point collides.
+GRIDS = {
+    "mixed": dict(n_levels=5, log2_hashmap_size=14),
+    "small_dense": dict(n_levels=6, log2_hashmap_size=19, base_resolution=4.0, per_level_scale=1.5),
+    "L16": dict(n_levels=16, log2_hashmap_size=10, base_resolution=2.0, per_level_scale=1.3),
+    "L1": dict(n_levels=1),
+    "tiny_hash": dict(n_levels=3, log2_hashmap_size=4, per_level_scale=2.0),
+}
+GRID_SIZES = {
+    "mixed": [4096, 13824, 16384, 16384, 16384],                   # dense LDS; dense 24^3, global; hashed, global
+    "small_dense": [64, 216, 736, 2744, 9264, 29792],              # 4^3, 6^3, 9^3 = 729, 14^3 in LDS; 21^3 = 9261, 31^3 = 29791 global
+    "L16": [8, 32, 64, 128, 216, 512, 1000] + [1024] * 9,          # 2^3, 3^3 = 27, 4^3, 5^3 = 125, 6^3, 8^3, 10^3 dense, then hashed
+    "L1": [4096],
+    "tiny_hash": [16, 16, 16],
+}
 
 
 def _f32(v):
@@ -93,3 +111,28 @@ def face_distance(x, **grid):
         fr = pos - torch.floor(pos)
         best = torch.minimum(best, torch.minimum(fr, 1.0 - fr).min(dim=1).values)
     return best
+
+
+def touch_sums(x, de, **grid):
+    """per table entry: the sum over the (point, corner) terms that add into it of |d_enc|, and the number of those terms
+    (float64, from the statement's corners)"""
+    lv, n = levels(**dict(SHIPPED, **grid))
+    out = torch.zeros(n // 4, 4, dtype=torch.float64)
+    cnt = torch.zeros(n // 4, dtype=torch.int64)
+    x = x.double()
+    for l, (s, res, size, off, hashed) in enumerate(lv):
+        gi = torch.floor(x * s + 0.5).long() & M32
+        for c in range(8):
+            idx = corner_index(gi[:, 0] + (c & 1), gi[:, 1] + ((c >> 1) & 1), gi[:, 2] + (c >> 2), res, size, hashed)
+            out.index_add_(0, off + idx, de[:, 4 * l:4 * l + 4].abs().double())
+            cnt.index_add_(0, off + idx, torch.ones_like(idx))
+    return out.reshape(-1), cnt.repeat_interleave(4)
+
+
+def rounding_bar(x_max=1.0, **grid):
+    """E_F: the most a kernel's cell fraction f = pos - floor(pos) is off.  pos = fmaf(scale, x, 0.5) is rounded to fp32 once: half
+    an ulp at |pos| <= pos_max = max_l scale_l * x_max + 0.5, i.e. 2^(floor(log2(pos_max)) - 24), plus 8 u (u = 2^-24) for the
+    few fp32 operations after it.  The shipped grid with x_max = 1 has pos_max = 212.7: 2^-17 + 8 u."""
+    lv, _ = levels(**dict(SHIPPED, **grid))
+    pos_max = max(s for s, *_ in lv) * x_max + 0.5
+    return 2.0 ** (math.floor(math.log2(pos_max)) - 24) + 8 * 2.0 ** -24

@@ -37,6 +37,47 @@ def test_library_level_table_matches_the_statement(lib_built):
         uvmap.hashgrid_levels(n_levels=17)
 
 
+@pytest.mark.parametrize("name", sorted(R.GRIDS))
+def test_library_level_table_matches_the_statement_off_the_shipped_grid(lib_built, name):
+    """Every grid of hashgrid_ref.GRIDS: the library's host arithmetic (exp2f / log2f in fp32) and the statement's agree field by
+    field, bit-equal scales included, and both give the row counts the grid was chosen for.  small_dense has scales that are
+    integers mathematically (3, 5, 8): an exp2f one ulp above would change res and every offset after it."""
+    from texgs import uvmap
+    grid = R.GRIDS[name]
+    got = uvmap.hashgrid_levels(**grid)
+    lv, n = R.levels(**dict(R.SHIPPED, **grid))
+    assert len(lv) == grid["n_levels"] == len(got["scale"])
+    assert got["n_params"] == n == 4 * sum(R.GRID_SIZES[name])
+    assert got["scale"] == [s for s, *_ in lv]                    # bit-equal fp32 scales
+    assert got["res"] == [r for _, r, *_ in lv]
+    assert got["size"] == [sz for _, _, sz, _, _ in lv] == R.GRID_SIZES[name]
+    assert got["offset"] == [o for _, _, _, o, _ in lv]
+    assert all(sz % 8 == 0 for sz in got["size"])
+    if name == "small_dense":
+        assert got["scale"][:5] == [3.0, 5.0, 8.0, 12.5, 19.25] and abs(got["scale"][5] - 29.375) < 1e-5
+        assert got["res"] == [4, 6, 9, 14, 21, 31]
+    if name == "mixed":
+        assert [h for *_, h in lv] == [False, False, True, True, True]
+
+
+def test_rounding_bar():
+    assert R.rounding_bar(1.0) == 2.0 ** -17 + 8 * 2.0 ** -24                  # the shipped grid: pos < 256
+    assert R.rounding_bar(1.15, **R.GRIDS["mixed"]) == 2.0 ** -18 + 8 * 2.0 ** -24     # 69.14 * 1.15 + 0.5 = 80.0: [64, 128)
+    assert R.rounding_bar(1.15, **R.GRIDS["small_dense"]) == 2.0 ** -19 + 8 * 2.0 ** -24       # 29.37 * 1.15 + 0.5 = 34.3
+    assert R.rounding_bar(1.15, **R.GRIDS["L1"]) == 2.0 ** -20 + 8 * 2.0 ** -24        # 15 * 1.15 + 0.5 = 17.75
+
+
+def test_touch_sums_by_hand():
+    # one point in the middle of cell (1, 2, 3) of the 16^3 level: its 8 corners are 8 distinct rows, each touched once
+    x = torch.tensor([[1.0 / 15, 2.0 / 15, 3.0 / 15]], dtype=torch.float64)
+    de = torch.tensor([[1.0, -2.0, 3.0, -4.0]])
+    T, cnt = R.touch_sums(x, de, **R.GRIDS["L1"])
+    rows = sorted((1 + (c & 1)) + 16 * (2 + ((c >> 1) & 1)) + 256 * (3 + (c >> 2)) for c in range(8))
+    assert sorted(set((cnt.nonzero()[:, 0] // 4).tolist())) == rows
+    assert int(cnt.sum()) == 8 * 4 and int(cnt.max()) == 1
+    assert T.reshape(-1, 4)[rows[0]].tolist() == [1.0, 2.0, 3.0, 4.0] and float(T.sum()) == 80.0
+
+
 def test_level0_is_dense():
     g = torch.randint(0, 16, (200, 3))
     idx = R.corner_index(g[:, 0], g[:, 1], g[:, 2], 16, 4096, False)
@@ -122,6 +163,23 @@ def test_stage3_checkpoint_inv_uv_net(lib_built):
     # the fixture's encoding is a 4096-value stand-in, not a shipped grid: refused with the count it needs
     with pytest.raises(ValueError, match="expected 131072"):
         uvmap.InvUVNet().load_reference_state(inv)
+
+
+def test_reference_state_of_another_grid_is_refused(lib_built):
+    """The table of a tiny-cuda-nn state is sized by its grid: a net built for one grid refuses the table of another, either way
+    round, with the count it needs, and keeps its own parameters."""
+    from texgs import uvmap
+    g = torch.Generator().manual_seed(2)
+    mixed = uvmap.InvUVNet(grid=R.GRIDS["mixed"])
+    assert mixed.encoding.n_params == 268288 and mixed.encoding.n_output_dims == 20
+    before = mixed.encoding.params.detach().clone()
+    with pytest.raises(ValueError, match="expected 268288"):
+        mixed.load_reference_state(_tcnn_state(torch.float32, g))                  # the shipped grid's 131072-value table
+    assert torch.equal(mixed.encoding.params.detach(), before) and not mixed.tcnn_layout_unpinned
+    st = _tcnn_state(torch.float32, g)
+    st["pre_mlp.0.params"] = torch.randn(268288, generator=g)
+    with pytest.raises(ValueError, match="expected 131072"):
+        uvmap.InvUVNet().load_reference_state(st)
 
 
 def test_wrong_sizes_raise_before_any_launch(lib_built):
