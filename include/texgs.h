@@ -416,6 +416,34 @@ int texgs_knn3_mean_dist2(const float* xyz, int32_t n, float* mean_d2, void* tem
 size_t texgs_fps_temp_bytes(int32_t n, int32_t k);
 int texgs_farthest_points(const float* xyz, int32_t n, int32_t k, int32_t start, int32_t* idx, void* temp, void* stream);
 
+/* ---- seamless cubemap sampling (additive in v18; csrc/cubetex.hip) ---------------------------------------------------------------
+ * tex f32[6, R, R, C] (faces +x, -x, +y, -y, +z, -z, channels last), dirs f32[N, 3] of any length, out f32[N, C].
+ * R >= 2, C >= 1, 6 R R C < 2^31, 0 <= N < 2^31 (N = 0: no launch).  Face and in-face coordinates as in the rasterizer: the face
+ * is the dominant axis (>= tie order x, y, z), col = (sc/ma + 1) R/2 - 0.5, row likewise, texel centres at (i + 0.5)/R.
+ *
+ * TEXGS_CUBE_LINEAR: the four bilinear taps around (floor(col), floor(row)).  A tap inside the face reads it; a tap with one
+ * coordinate out of range (at -1 or R) reads the face across that edge, at the same position along the edge; a tap with both out
+ * of range is a cube corner and is dropped, the other three weights divided by their sum.
+ * TEXGS_CUBE_NEAREST: texel (floor(col + 0.5), floor(row + 0.5)) clamped into the face.
+ * tap_map != 0: every tap t becomes clamp(0.28209479177387814 t + 0.5, 0, 1) (sh02rgb) BEFORE the filter.
+ * A zero or non-finite direction gives a zero output row and zero gradients (decided in the kernel). */
+#define TEXGS_CUBE_LINEAR 0
+#define TEXGS_CUBE_NEAREST 1
+int texgs_cube_sample(const float* tex, int32_t R, int32_t C, const float* dirs, int32_t N, int32_t filter, int32_t tap_map,
+                      float* out, void* stream);
+/* The same fetch (linear) at the directions of NVDIFFREC/util.py:119-133 cubemap_to_latlong, computed in the kernel: out f32[H, W, C],
+ * pixel (i, j) looks along (sin(th) sin(ph), cos(th), -sin(th) cos(ph)), th = pi gy_i, ph = pi gx_j,
+ * gy = linspace(1/H, 1 - 1/H, H), gx = linspace(-1 + 1/W, 1 - 1/W, W).  H, W >= 1, H W < 2^31. */
+int texgs_cube_latlong(const float* tex, int32_t R, int32_t C, int32_t H, int32_t W, int32_t tap_map, float* out, void* stream);
+/* Backward of the linear fetch without tap_map, g_out f32[N, C].  d_tex f32[6, R, R, C] or NULL: w_tap g_out is ADDED with fp32
+ * atomics (the caller zeroes it; the sum's order, so its last bits, vary from run to run).  d_dirs f32[N, 3] or NULL: the exact
+ * derivative with respect to the raw direction, written (the renormalised corner weights included). */
+int texgs_cube_sample_backward(const float* tex, int32_t R, int32_t C, const float* dirs, int32_t N, const float* g_out,
+                               float* d_tex, float* d_dirs, void* stream);
+/* Backward of the nearest fetch: g_out is ADDED to d_tex at each query's texel (atomics, as above). */
+int texgs_cube_sample_nearest_backward(int32_t R, int32_t C, const float* dirs, int32_t N, const float* g_out, float* d_tex,
+                                       void* stream);
+
 /* Hardware self-test of the wave64 cross-lane primitives the backward's reductions use (csrc/wave_ops.h: DPP lane^4 /
  * lane^8 exchanges, permlane16/32 swaps, both transposing butterflies).  seed: f32[128] device; out: f32[576] device,
  * nine blocks of 64 differences against the __shfl_xor formulation -- all exactly 0 on gfx950. */

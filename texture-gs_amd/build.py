@@ -30,6 +30,7 @@ UNITS = {
     "uvnet.hip": [],
     "uvmap.hip": ["-munsafe-fp-atomics"],
     "points.hip": ["-ffp-contract=off"],      # its squared distance is a bit-exact contract: no fused multiply-add
+    "cubetex.hip": ["-munsafe-fp-atomics"],   # the texture gradient's scatter: hardware fp32 atomic adds
     "abi.hip": [],
 }
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "wave_ops.h"), os.path.join(CSRC, "render_bwd_body.h"),

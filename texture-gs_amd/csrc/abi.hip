@@ -504,6 +504,53 @@ int texgs_farthest_points(const float* xyz, int32_t n, int32_t k, int32_t start,
     return 0;
 }
 
+static int cube_shape_ok(int32_t R, int32_t C) {
+    if (R < 2) return fail_msg("R < 2: a cubemap face needs at least 2 x 2 texels");
+    if (C < 1) return fail_msg("C < 1");
+    if (6ll * R * R * C >= (1ll << 31)) return fail_msg("6 R R C must be below 2^31");
+    return 0;
+}
+
+int texgs_cube_sample(const float* tex, int32_t R, int32_t C, const float* dirs, int32_t N, int32_t filter, int32_t tap_map,
+                      float* out, void* stream) {
+    if (int r = cube_shape_ok(R, C)) return r;
+    if (N < 0) return fail_msg("N < 0");
+    if (filter != TEXGS_CUBE_LINEAR && filter != TEXGS_CUBE_NEAREST) return fail_msg("filter must be TEXGS_CUBE_LINEAR or TEXGS_CUBE_NEAREST");
+    if (!tex || (N > 0 && (!dirs || !out))) return fail_msg("NULL argument");
+    if (int r = launch_cube_sample(tex, R, C, dirs, N, filter, tap_map, out, (hipStream_t)stream)) return fail("cube_sample", (hipError_t)r);
+    return 0;
+}
+
+int texgs_cube_latlong(const float* tex, int32_t R, int32_t C, int32_t H, int32_t W, int32_t tap_map, float* out, void* stream) {
+    if (int r = cube_shape_ok(R, C)) return r;
+    if (H < 1 || W < 1) return fail_msg("H and W must be positive");
+    if ((long long)H * W >= (1ll << 31)) return fail_msg("H W must be below 2^31");
+    if (!tex || !out) return fail_msg("NULL argument");
+    if (int r = launch_cube_latlong(tex, R, C, H, W, tap_map, out, (hipStream_t)stream)) return fail("cube_latlong", (hipError_t)r);
+    return 0;
+}
+
+int texgs_cube_sample_backward(const float* tex, int32_t R, int32_t C, const float* dirs, int32_t N, const float* g_out,
+                               float* d_tex, float* d_dirs, void* stream) {
+    if (int r = cube_shape_ok(R, C)) return r;
+    if (N < 0) return fail_msg("N < 0");
+    if (!d_tex && !d_dirs) return fail_msg("d_tex and d_dirs are both NULL: nothing to compute");
+    if ((d_dirs && !tex) || (N > 0 && (!dirs || !g_out))) return fail_msg("NULL argument");
+    if (int r = launch_cube_sample_backward(tex, R, C, dirs, N, g_out, d_tex, d_dirs, (hipStream_t)stream))
+        return fail("cube_sample_backward", (hipError_t)r);
+    return 0;
+}
+
+int texgs_cube_sample_nearest_backward(int32_t R, int32_t C, const float* dirs, int32_t N, const float* g_out, float* d_tex,
+                                       void* stream) {
+    if (int r = cube_shape_ok(R, C)) return r;
+    if (N < 0) return fail_msg("N < 0");
+    if (!d_tex || (N > 0 && (!dirs || !g_out))) return fail_msg("NULL argument");
+    if (int r = launch_cube_sample_nearest_backward(R, C, dirs, N, g_out, d_tex, (hipStream_t)stream))
+        return fail("cube_sample_nearest_backward", (hipError_t)r);
+    return 0;
+}
+
 int texgs_selftest_waveops(const float* seed128, float* out576, void* stream) {
     if (!seed128 || !out576) return fail_msg("NULL argument");
     launch_selftest_waveops(seed128, out576, (hipStream_t)stream);

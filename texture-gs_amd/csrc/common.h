@@ -104,3 +104,8 @@ size_t knn3_temp_bytes(int n);
 int launch_knn3_mean_dist2(const float* xyz, int n, float* mean_d2, void* temp, hipStream_t s);
 size_t fps_temp_bytes(int n, int k);
 int launch_farthest_points(const float* xyz, int n, int k, int start, int32_t* idx, void* temp, hipStream_t s);
+int launch_cube_sample(const float* tex, int R, int C, const float* dirs, int N, int filter, int tap_map, float* out, hipStream_t s);
+int launch_cube_latlong(const float* tex, int R, int C, int H, int W, int tap_map, float* out, hipStream_t s);
+int launch_cube_sample_backward(const float* tex, int R, int C, const float* dirs, int N, const float* g_out, float* d_tex,
+                                float* d_dirs, hipStream_t s);
+int launch_cube_sample_nearest_backward(int R, int C, const float* dirs, int N, const float* g_out, float* d_tex, hipStream_t s);

@@ -81,7 +81,8 @@ EXPORTS = ["texgs_abi_version", "texgs_build_id", "texgs_last_error", "texgs_sca
            "texgs_uv_pack_bf16x3", "texgs_uv_taylor_packed_bf16x3", "texgs_uv_backward", "texgs_uv_backward_mixed", "texgs_uv_backward_temp_bytes", "texgs_uv_pack_mixed", "texgs_uv_taylor_packed_mixed",
            "texgs_hashgrid_levels", "texgs_hashgrid_forward", "texgs_hashgrid_backward_temp_bytes", "texgs_hashgrid_backward",
            "texgs_chamfer_nn_temp_bytes", "texgs_chamfer_nn",
-           "texgs_knn3_temp_bytes", "texgs_knn3_mean_dist2", "texgs_fps_temp_bytes", "texgs_farthest_points"]
+           "texgs_knn3_temp_bytes", "texgs_knn3_mean_dist2", "texgs_fps_temp_bytes", "texgs_farthest_points",
+           "texgs_cube_sample", "texgs_cube_latlong", "texgs_cube_sample_backward", "texgs_cube_sample_nearest_backward"]
 KERNEL_NAMES = ["preprocess_fwd", "scan", "duplicate", "sort", "ranges", "render_fwd", "render_bwd", "preprocess_bwd",
                 "texgrad_reduce"]
 
@@ -98,6 +99,10 @@ def load():
             f"libtexgs.so not found at {LIB_PATH}: build it with `python texture-gs_amd/build.py` "
             "(hipcc --offload-arch=gfx950). There is no CPU fallback for the rasterizer.")
     lib = C.CDLL(LIB_PATH)
+    missing = [n for n in EXPORTS if not hasattr(lib, n)]
+    if missing:         # a library from before an additive change of the ABI (the version number stays): same advice as a stale version
+        raise RuntimeError(f"libtexgs.so at {LIB_PATH} does not export {', '.join(missing)}; rebuild it with "
+                           "`python texture-gs_amd/build.py`")
     P = C.POINTER
     lib.texgs_abi_version.restype = C.c_int
     lib.texgs_last_error.restype = C.c_char_p
@@ -173,6 +178,15 @@ def load():
     lib.texgs_fps_temp_bytes.restype = C.c_size_t
     lib.texgs_farthest_points.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.texgs_farthest_points.restype = C.c_int
+    lib.texgs_cube_sample.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.texgs_cube_sample.restype = C.c_int
+    lib.texgs_cube_latlong.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.texgs_cube_latlong.restype = C.c_int
+    lib.texgs_cube_sample_backward.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_void_p]
+    lib.texgs_cube_sample_backward.restype = C.c_int
+    lib.texgs_cube_sample_nearest_backward.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.texgs_cube_sample_nearest_backward.restype = C.c_int
     lib.texgs_selftest_waveops.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     lib.texgs_selftest_waveops.restype = C.c_int
     lib.texgs_profile_enable.argtypes = [C.c_int]
