@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define TEXGS_ABI_VERSION 18
+#define TEXGS_ABI_VERSION 19
 #define TEXGS_TILE 16          /* 16x16 pixel tiles, one 256-thread workgroup (4 wave64) per tile     */
 #define TEXGS_REC_TEST_FLOATS 8    /* per-Gaussian TEST record (32 B): what the per-block culls and the alpha test read  */
 #define TEXGS_REC_SHADE_FLOATS 20  /* per-Gaussian SHADING record (80 B): fetched only for Gaussians that survive a cull (one record per
@@ -310,7 +310,7 @@ int texgs_norm_from_depth(const float* depth, const float* viewmatrix, float tan
  * UVNet.forward (models/modules/uv_net.py:19-36) + torch.autograd.functional.jacobian (models/texture_gaussian3d.py:216-227).
  * Weights are nn.Linear tensors (row-major [out, in]) of the shipped architecture (hidden width 128): pre_mlp = W1, W2;
  * mlp = W3, W4, W5; biases may be NULL (tiny-cuda-nn networks have none); emb f32[128] is geo_emb.weight[0]; xyz_offset /
- * xyz_scale f32[3] or NULL.  uvs f32[N,3] (unit), grad_uvs f32[N,9] with [3*i+j] = d uv_i / d x_j.  fp32 MFMA. */
+ * xyz_scale f32[3] or NULL.  uvs f32[N,3] (unit), grad_uvs f32[N,9] with [3*i+j] = d uv_i / d x_j. */
 typedef struct TexGSUVNet {
     const float *W1, *b1;      /* [128,3], [128]   */
     const float *W2, *b2;      /* [128,128], [128] */
@@ -320,29 +320,24 @@ typedef struct TexGSUVNet {
     const float *xyz_offset, *xyz_scale;
     int32_t hidden;            /* must be 128      */
 } TexGSUVNet;
-size_t texgs_uv_taylor_temp_bytes(void);
-int texgs_uv_taylor(const TexGSUVNet* net, const float* xyz, int32_t N, float* uvs, float* grad_uvs, void* temp, void* stream);
-/* The same in two steps, for callers that evaluate one set of weights many times (every view of a retexture / viewer session,
- * every forward between two optimizer steps): texgs_uv_pack re-orders W2..W4 for the matrix cores into `packed`
- * (texgs_uv_taylor_temp_bytes() bytes) once, texgs_uv_taylor_packed evaluates with it. */
-int texgs_uv_pack(const TexGSUVNet* net, void* packed, void* stream);
-int texgs_uv_taylor_packed(const TexGSUVNet* net, const void* packed, const float* xyz, int32_t N, float* uvs, float* grad_uvs,
-                           void* stream);
-/* The same two steps at SPLIT-bf16 precision (v12, opt-in): every operand of the three 128x128 layers is split into two bf16
- * halves and a product taken as hi*hi + hi*lo + lo*hi on the bf16 matrix cores (f32 accumulation) -- ~2.5x faster than the f32-
- * input MFMA of texgs_uv_taylor_packed, uvs / Jacobian within ~2e-5 of it.  `packed` has the same size, a different layout: a
- * buffer packed by one variant must not be handed to the other. */
-int texgs_uv_pack_bf16x3(const TexGSUVNet* net, void* packed, void* stream);
-int texgs_uv_taylor_packed_bf16x3(const TexGSUVNet* net, const void* packed, const float* xyz, int32_t N, float* uvs, float* grad_uvs,
-                                  void* stream);
-
-/* The same two steps with the VALUE column on the f32-input MFMA and the three TANGENT columns at split-bf16 precision (v14,
- * opt-in): uvs and every ReLU mask are those of texgs_uv_taylor_packed (the value column decides everything discrete and runs
- * exactly as there); the Jacobian is within ~1e-5 relative of it; ~2x faster.  `packed` holds BOTH layouts back to back:
- * 2 * texgs_uv_taylor_temp_bytes() bytes. */
-int texgs_uv_pack_mixed(const TexGSUVNet* net, void* packed, void* stream);
-int texgs_uv_taylor_packed_mixed(const TexGSUVNet* net, const void* packed, const float* xyz, int32_t N, float* uvs, float* grad_uvs,
-                                 void* stream);
+/* `precision` (v19) selects the arithmetic of the three 128x128 layers; a point's four columns are the value and three tangents:
+ *   TEXGS_UV_FP32    every column on the f32-input MFMA (exact f32 products);
+ *   TEXGS_UV_BF16X3  every operand split into two bf16 halves and a product taken as hi*hi + hi*lo + lo*hi on the bf16 matrix
+ *                    cores (f32 accumulation): ~2.5x faster, uvs / Jacobian within ~2e-5 of FP32; the ReLU masks come from the
+ *                    split value column (inference only);
+ *   TEXGS_UV_MIXED   the VALUE column as FP32 -- uvs and every ReLU mask are FP32's bit for bit: the value column decides
+ *                    everything discrete --, the three TANGENT columns as BF16X3: the Jacobian within ~1e-5 relative, ~2x faster.
+ * Any other value is an error (no launch). */
+enum { TEXGS_UV_FP32 = 0, TEXGS_UV_BF16X3 = 1, TEXGS_UV_MIXED = 2 };
+/* Two steps, for callers that evaluate one set of weights many times (every view of a retexture / viewer session, every
+ * forward between two optimizer steps): texgs_uv_pack re-orders W2..W4 for the matrix cores into `packed`
+ * (texgs_uv_packed_bytes(precision) bytes: 196608, 196608, 393216; 0 for an unknown precision) once, texgs_uv_taylor_packed
+ * evaluates with it (N = 0: nothing is launched, xyz / uvs / grad_uvs may be NULL).  The layout depends on the precision: a
+ * buffer packed for one must not be handed to another. */
+size_t texgs_uv_packed_bytes(int32_t precision);
+int texgs_uv_pack(const TexGSUVNet* net, int32_t precision, void* packed, void* stream);
+int texgs_uv_taylor_packed(const TexGSUVNet* net, int32_t precision, const void* packed, const float* xyz, int32_t N, float* uvs,
+                           float* grad_uvs, void* stream);
 
 /* Backward of the UV map (v13): gradients of uvs = UVNet(xyz) w.r.t. every weight, bias and the embedding for an upstream
  * gradient g_uvs f32[N,3] -- what loss.backward() does through models/modules/uv_net.py:19-36 in the reference (autograd over
@@ -350,7 +345,10 @@ int texgs_uv_taylor_packed_mixed(const TexGSUVNet* net, const void* packed, cons
  * (activations recomputed per tile of 64 points in LDS, the three 128x128 weight gradients in registers, fp32 MFMA) + a
  * deterministic reduction of its <= 256 partial sums.  Outputs are nn.Linear-shaped, OVERWRITTEN (not accumulated); a NULL
  * pointer skips that gradient; d emb = db2 (the embedding is added where b2 is).  d xyz is not produced here: it is J^T g with
- * the Jacobian texgs_uv_taylor already returned.  temp: texgs_uv_backward_temp_bytes(N) bytes. */
+ * the Jacobian texgs_uv_taylor_packed already returned.  temp: texgs_uv_backward_temp_bytes(N) bytes.
+ * precision TEXGS_UV_FP32: all nine GEMMs on the f32-input MFMA.  Otherwise the six GEMMs of the backward chain (W^T d, d h^T)
+ * are split-bf16 products (three bf16 MFMAs per f32 product, f32 accumulation: ~1e-5 relative); the forward recomputation stays
+ * on the f32-input MFMA, so the ReLU masks are those of the FP32 / MIXED forward launch bit for bit. */
 typedef struct TexGSUVNetGrad {
     float *dW1, *db1;          /* [128,3], [128]   */
     float *dW2, *db2;          /* [128,128], [128] */
@@ -358,13 +356,8 @@ typedef struct TexGSUVNetGrad {
     float *dW5, *db5;          /* [3,128], [3]     */
 } TexGSUVNetGrad;
 size_t texgs_uv_backward_temp_bytes(int32_t N);
-int texgs_uv_backward(const TexGSUVNet* net, const float* xyz, const float* g_uvs, int32_t N, const TexGSUVNetGrad* out, void* temp,
-                      void* stream);
-/* The same gradients with the six GEMMs of the backward chain (W^T d, d h^T) as split-bf16 products (three bf16 MFMAs per f32
- * product, f32 accumulation: ~1e-5 relative); the forward recomputation stays on the f32-input MFMA, so the ReLU masks are those
- * of the forward launch bit for bit (v15; same arguments and temp size). */
-int texgs_uv_backward_mixed(const TexGSUVNet* net, const float* xyz, const float* g_uvs, int32_t N, const TexGSUVNetGrad* out, void* temp,
-                            void* stream);
+int texgs_uv_backward(const TexGSUVNet* net, int32_t precision, const float* xyz, const float* g_uvs, int32_t N, const TexGSUVNetGrad* out,
+                      void* temp, void* stream);
 
 /* ---- UV-map stage (v16): models/uv_map_gaussian3d.py:167-238 ----
  * Multiresolution hash-grid encoding of InvUVNet (tiny-cuda-nn "HashGrid", models/modules/utils.py:5-29; index rules restated

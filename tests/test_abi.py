@@ -98,3 +98,34 @@ def test_num_rendered_reduce_is_host_only_arithmetic(lib_built):
     assert lib.texgs_num_rendered_reduce(big.ctypes.data, 512, C.byref(d), None) != 0
     assert b"2^32" in lib.texgs_last_error()
     assert lib.texgs_num_rendered_reduce(None, 4, C.byref(d), None) != 0
+
+
+def test_uv_precision_is_checked_before_any_launch(lib_built):
+    """The UV map's entry points take the precision as an argument (v19): texgs_uv_packed_bytes sizes the packed weights per precision,
+    and a value outside TEXGS_UV_FP32 / _BF16X3 / _MIXED is refused by name before anything is launched (no GPU is needed to see it;
+    a launch here would fail with a HIP error that does not name the argument)."""
+    import ctypes as C
+    sys.path.insert(0, os.path.join(ROOT, "texture-gs_amd"))
+    from texgs import _lib
+    lib = _lib.load()
+    assert [lib.texgs_uv_packed_bytes(p) for p in (0, 1, 2)] == [196608, 196608, 393216]
+    assert (_lib.UV_PRECISION["fp32"], _lib.UV_PRECISION["bf16x3"], _lib.UV_PRECISION["mixed"]) == (0, 1, 2)
+    assert lib.texgs_uv_packed_bytes(3) == 0 and lib.texgs_uv_packed_bytes(-1) == 0
+    net = _lib.UVNetStruct(*([None] * 13), 128)
+    grads = _lib.UVNetGradStruct(*([None] * 10))
+    buf = (C.c_float * 64)()          # stands in for every device buffer: nothing may read it
+    b = C.addressof(buf)
+    for bad in (3, -1):
+        calls = {"texgs_uv_pack": lambda: lib.texgs_uv_pack(C.byref(net), bad, b, None),
+                 "texgs_uv_taylor_packed": lambda: lib.texgs_uv_taylor_packed(C.byref(net), bad, b, b, 4, b, b, None),
+                 "texgs_uv_backward": lambda: lib.texgs_uv_backward(C.byref(net), bad, b, b, 4, C.byref(grads), b, None)}
+        for name, call in calls.items():
+            assert lib.texgs_num_rendered_reduce(None, 4, None, None) != 0 and b"precision" not in lib.texgs_last_error()     # another message first
+            assert call() != 0, (name, bad)
+            assert b"precision" in lib.texgs_last_error(), (name, bad, lib.texgs_last_error())
+    # N = 0 is a no-op whose point / output pointers may be NULL (an empty tensor's data pointer is); N < 0 is refused
+    net = _lib.UVNetStruct(*([b] * 13), 128)
+    for prec in (0, 1, 2):
+        assert lib.texgs_uv_taylor_packed(C.byref(net), prec, b, None, 0, None, None, None) == 0, prec
+        assert lib.texgs_uv_taylor_packed(C.byref(net), prec, b, None, -1, None, None, None) != 0, prec
+        assert lib.texgs_uv_taylor_packed(C.byref(net), prec, b, None, 4, b, b, None) != 0 and b"NULL" in lib.texgs_last_error(), prec

@@ -205,7 +205,7 @@ def test_header_declares_the_entry_points():
     hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
     for name in ENTRY_POINTS:
         assert re.search(r"\bint\s+%s\s*\(\s*const float\*\s*tex,\s*int32_t R,\s*int32_t C," % name, hdr), name
-    assert re.search(r"#define\s+TEXGS_ABI_VERSION\s+18\b", hdr)       # purely additive: the version stays
+    assert re.search(r"#define\s+TEXGS_ABI_VERSION\s+19\b", hdr)
 
 
 def test_nvdiffrast_drop_in_refuses_what_it_does_not_do():

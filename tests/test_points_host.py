@@ -155,5 +155,5 @@ def test_header_and_abi_version(lib_built):
         assert re.search(r"\b%s\s*\(" % name, hdr), name
         assert name in _lib.EXPORTS
         assert hasattr(_lib.load(), name)
-    assert re.search(r"#define\s+TEXGS_ABI_VERSION\s+18\b", hdr)
-    assert _lib.load().texgs_abi_version() == _lib.ABI_VERSION == 18
+    assert re.search(r"#define\s+TEXGS_ABI_VERSION\s+19\b", hdr)
+    assert _lib.load().texgs_abi_version() == _lib.ABI_VERSION == 19

@@ -212,9 +212,10 @@ def test_mixed_precision_kernel_keeps_value_column_exact(lib_built):
     Hh.report("uv_taylor_mixed/300k", uvs_max_abs_vs_f32_kernel=d_uv, uvs_bit_identical_frac=same, J_max_over_Jmax_vs_f32_kernel_all_points=d_J_max,
               J_p9999_over_Jmax=d_J_p9999, J_rel_l2_vs_f32_kernel_all_points=rel_all, us_fp32=times["fp32"], us_mixed=times["mixed"])
     # the first layer and the bias / embedding adds are written with explicit roundings shared by all kernels of csrc/uvnet.hip, the
-    # 128x128 layers' value column is the same MFMA sequence: same pre-activations, same masks, same uvs (up to how the compiler
-    # contracts the 128 -> 3 layer's sums); the Jacobian differs by the tangents' split-bf16 arithmetic only -- at EVERY point
-    assert d_uv < 2.5e-7, d_uv
+    # 128x128 layers' value column is the same MFMA sequence and the 128 -> 3 layer's value sum is one function with its roundings
+    # written out (uv_out_f32): same pre-activations, same masks, the same uvs bit for bit; the Jacobian differs by the tangents'
+    # split-bf16 arithmetic only -- at EVERY point
+    assert d_uv == 0.0 and same == 1.0, (d_uv, same)
     assert d_J_max < 1e-4 and rel_all < 2e-5, (d_J_max, rel_all)
     with torch.no_grad():
         nm.mlp[0].weight.mul_(1.5)
@@ -222,6 +223,73 @@ def test_mixed_precision_kernel_keeps_value_column_exact(lib_built):
     um2, _ = nm.uv_and_jacobian(xyz, embd)
     u32b, _ = n32.uv_and_jacobian(xyz, embd)
     assert float((um2 - u32b).abs().max()) < 1e-6 and float((um2 - um).abs().max()) > 1e-3
+
+
+def _raw_uv_call(net, emb, xyz, pad_rows=32, sentinel=-7.5):
+    """texgs_uv_pack + texgs_uv_taylor_packed on output buffers that are `pad_rows` rows longer than N and pre-filled: -> the whole buffers."""
+    import ctypes as C
+    from texgs import _lib
+    lib = _lib.load()
+    dev = xyz.device
+    p = lambda t: None if t is None else t.data_ptr()
+    ws = net._kernel_args(dev, emb)
+    st = _lib.UVNetStruct(*[p(t) for t in ws], 128)
+    prec = _lib.UV_PRECISION[net.precision]
+    x = xyz.contiguous()
+    n = x.shape[0]
+    packed = torch.empty(lib.texgs_uv_packed_bytes(prec), dtype=torch.uint8, device=dev)
+    uvs = torch.full((n + pad_rows, 3), sentinel, dtype=torch.float32, device=dev)
+    J = torch.full((n + pad_rows, 9), sentinel, dtype=torch.float32, device=dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    _lib.check(lib.texgs_uv_pack(C.byref(st), prec, p(packed), stream), "texgs_uv_pack")
+    _lib.check(lib.texgs_uv_taylor_packed(C.byref(st), prec, p(packed), p(x), n, p(uvs), p(J), stream), "texgs_uv_taylor_packed")
+    torch.cuda.synchronize()
+    return uvs, J
+
+
+@pytest.mark.gpu
+def test_ragged_tiles_depend_on_their_own_point_only(lib_built):
+    """N that is no multiple of the 32-point tile, in every precision: a point's uvs / J come from its own MFMA column alone, so a call
+    on a prefix or on a slice of 97 points returns bit for bit the rows of the 97-point call (the columns past N repeat point N - 1 and
+    must neither leak into a live column nor be written: rows past N of an over-allocated output keep their fill); uvs within the
+    full-size tests' bars of float64 torch; N = 0 returns empty tensors; "mixed" has the f32 kernel's uvs."""
+    dev = torch.device("cuda:0")
+    torch.manual_seed(11)
+    kw = dict(xyz_offset=[0.1, -0.2, 0.05], xyz_scale=[1.5, 0.8, 1.2])
+    net = UVNet(precision="fp32", **kw)
+    emb = torch.randn(128) * 0.2
+    g = torch.Generator().manual_seed(1)
+    xyz = torch.randn(97, 3, generator=g)
+    xyz = xyz / xyz.norm(dim=1, keepdim=True) * (1 + 0.02 * torch.randn(97, 1, generator=g))
+    net64 = UVNet(**kw).double()
+    net64.load_state_dict({k: v.double() for k, v in net.state_dict().items()})
+    with torch.no_grad():
+        ref_uv = net64(xyz.double(), emb.double())
+    xd, embd = xyz.to(dev), emb.to(dev)
+    subsets = [slice(0, n) for n in (1, 31, 32, 33, 64, 65)] + [slice(5, 70)]
+    full = {}
+    for precision, bar in (("fp32", 5e-6), ("mixed", 5e-6), ("bf16x3", 2e-5)):
+        m = UVNet(precision=precision, **kw).to(dev)
+        m.load_state_dict(net.state_dict())
+        uvs, J = _raw_uv_call(m, embd, xd)
+        assert bool((uvs[97:] == -7.5).all()) and bool((J[97:] == -7.5).all()), precision
+        uvs, J = uvs[:97], J[:97]
+        full[precision] = uvs
+        e_uv = float((uvs.cpu().double() - ref_uv).abs().max())
+        Hh.report(f"uv_taylor/ragged/{precision}", uvs_max_abs_err=e_uv)
+        assert e_uv < bar, (precision, e_uv)
+        for sl in subsets:
+            n = sl.stop - sl.start
+            u, j = _raw_uv_call(m, embd, xd[sl])
+            assert torch.equal(u[:n], uvs[sl]) and torch.equal(j[:n], J[sl]), (precision, sl)
+            assert bool((u[n:] == -7.5).all()) and bool((j[n:] == -7.5).all()), (precision, sl)
+        u0, j0 = m.uv_and_jacobian(xd[:0], embd)
+        assert u0.shape == (0, 3) and j0.shape == (0, 9), precision
+        ua, ja = m.uv_and_jacobian(xd, embd)                # the module's path returns the same rows
+        assert torch.equal(ua, uvs) and torch.equal(ja, J), precision
+    d_uv = float((full["mixed"] - full["fp32"]).abs().max())
+    Hh.report("uv_taylor/ragged/mixed_vs_fp32", uvs_max_abs=d_uv)
+    assert d_uv == 0.0, d_uv
 
 
 def test_tcnn_flat_params_round_trip_and_first_layer_bias():
@@ -381,7 +449,7 @@ def test_fused_backward_kernel_vs_float64(lib_built, n, bias, norm, precision):
     dev = torch.device("cuda:0")
     torch.manual_seed(11 + n)
     kw = dict(xyz_offset=[0.1, -0.2, 0.05], xyz_scale=[1.5, 0.8, 1.2]) if norm else {}
-    net = UVNet(precision=precision, **kw)       # "mixed": the backward chain's six GEMMs as split-bf16 products (texgs_uv_backward_mixed)
+    net = UVNet(precision=precision, **kw)       # "mixed": the backward chain's six GEMMs as split-bf16 products (texgs_uv_backward, precision != FP32)
     if not bias:
         with torch.no_grad():
             for lin in net._linears():

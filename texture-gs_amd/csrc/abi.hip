@@ -316,95 +316,44 @@ int texgs_norm_from_depth(const float* depth, const float* viewmatrix, float tan
     return e == hipSuccess ? 0 : fail("norm_from_depth", e);
 }
 
-size_t texgs_uv_taylor_temp_bytes(void) { return uv_taylor_temp_bytes(); }
-
-int texgs_uv_taylor(const TexGSUVNet* net, const float* xyz, int32_t N, float* uvs, float* grad_uvs, void* temp, void* stream) {
-    if (!net || !xyz || !uvs || !grad_uvs || !temp) return fail_msg("NULL argument");
-    if (net->hidden != 128) return fail_msg("texgs_uv_taylor supports the shipped UVNet shape only (hidden width 128)");
-    if (!net->W1 || !net->W2 || !net->W3 || !net->W4 || !net->W5 || !net->emb) return fail_msg("weight pointer is NULL");
-    if (N < 0) return fail_msg("N < 0");
-    if (int r = launch_uv_taylor(net, xyz, N, uvs, grad_uvs, temp, (hipStream_t)stream)) return fail("uv_taylor", (hipError_t)r);
-    return 0;
-}
-
-static int check_uvnet(const TexGSUVNet* net) {
-    if (net->hidden != 128) return fail_msg("texgs_uv_taylor supports the shipped UVNet shape only (hidden width 128)");
+static int check_uvnet(const TexGSUVNet* net, int32_t precision) {
+    if (precision != TEXGS_UV_FP32 && precision != TEXGS_UV_BF16X3 && precision != TEXGS_UV_MIXED)
+        return fail_msg("precision must be TEXGS_UV_FP32, TEXGS_UV_BF16X3 or TEXGS_UV_MIXED");
+    if (net->hidden != 128) return fail_msg("the UV-map kernels support the shipped UVNet shape only (hidden width 128)");
     if (!net->W1 || !net->W2 || !net->W3 || !net->W4 || !net->W5 || !net->emb) return fail_msg("weight pointer is NULL");
     return 0;
 }
 
-int texgs_uv_pack(const TexGSUVNet* net, void* packed, void* stream) {
+size_t texgs_uv_packed_bytes(int32_t precision) { return uv_packed_bytes(precision); }
+
+int texgs_uv_pack(const TexGSUVNet* net, int32_t precision, void* packed, void* stream) {
     if (!net || !packed) return fail_msg("NULL argument");
-    if (int r = check_uvnet(net)) return r;
-    if (int r = launch_uv_pack(net, packed, (hipStream_t)stream)) return fail("uv_pack", (hipError_t)r);
+    if (int r = check_uvnet(net, precision)) return r;
+    if (int r = launch_uv_pack(net, precision, packed, (hipStream_t)stream)) return fail("uv_pack", (hipError_t)r);
     return 0;
 }
 
-int texgs_uv_taylor_packed(const TexGSUVNet* net, const void* packed, const float* xyz, int32_t N, float* uvs, float* grad_uvs,
-                           void* stream) {
-    if (!net || !packed || !xyz || !uvs || !grad_uvs) return fail_msg("NULL argument");
-    if (int r = check_uvnet(net)) return r;
-    if (N < 0) return fail_msg("N < 0");
-    if (int r = launch_uv_taylor_packed(net, packed, xyz, N, uvs, grad_uvs, (hipStream_t)stream)) return fail("uv_taylor", (hipError_t)r);
-    return 0;
-}
-
-int texgs_uv_pack_bf16x3(const TexGSUVNet* net, void* packed, void* stream) {
+int texgs_uv_taylor_packed(const TexGSUVNet* net, int32_t precision, const void* packed, const float* xyz, int32_t N, float* uvs,
+                           float* grad_uvs, void* stream) {
     if (!net || !packed) return fail_msg("NULL argument");
-    if (int r = check_uvnet(net)) return r;
-    if (int r = launch_uv_pack_bf16x3(net, packed, (hipStream_t)stream)) return fail("uv_pack_bf16x3", (hipError_t)r);
-    return 0;
-}
-
-int texgs_uv_taylor_packed_bf16x3(const TexGSUVNet* net, const void* packed, const float* xyz, int32_t N, float* uvs, float* grad_uvs,
-                                  void* stream) {
-    if (!net || !packed || !xyz || !uvs || !grad_uvs) return fail_msg("NULL argument");
-    if (int r = check_uvnet(net)) return r;
+    if (int r = check_uvnet(net, precision)) return r;
     if (N < 0) return fail_msg("N < 0");
-    if (int r = launch_uv_taylor_packed_bf16x3(net, packed, xyz, N, uvs, grad_uvs, (hipStream_t)stream)) return fail("uv_taylor_bf16x3", (hipError_t)r);
-    return 0;
-}
-
-// (declared here, not in common.h: csrc/uvnet.hip's mixed-precision launchers -- C++ linkage like the rest of common.h's)
-extern "C++" {
-int launch_uv_pack_mixed(const TexGSUVNet* net, void* packed, hipStream_t s);
-int launch_uv_taylor_packed_mixed(const TexGSUVNet* net, const void* packed, const float* xyz, int N, float* uvs, float* grad_uvs, hipStream_t s);
-}
-
-int texgs_uv_pack_mixed(const TexGSUVNet* net, void* packed, void* stream) {
-    if (!net || !packed) return fail_msg("NULL argument");
-    if (int r = check_uvnet(net)) return r;
-    if (int r = launch_uv_pack_mixed(net, packed, (hipStream_t)stream)) return fail("uv_pack_mixed", (hipError_t)r);
-    return 0;
-}
-
-int texgs_uv_taylor_packed_mixed(const TexGSUVNet* net, const void* packed, const float* xyz, int32_t N, float* uvs, float* grad_uvs,
-                                 void* stream) {
-    if (!net || !packed || !xyz || !uvs || !grad_uvs) return fail_msg("NULL argument");
-    if (int r = check_uvnet(net)) return r;
-    if (N < 0) return fail_msg("N < 0");
-    if (int r = launch_uv_taylor_packed_mixed(net, packed, xyz, N, uvs, grad_uvs, (hipStream_t)stream)) return fail("uv_taylor_mixed", (hipError_t)r);
+    if (N > 0 && (!xyz || !uvs || !grad_uvs)) return fail_msg("NULL argument");   /* (an empty tensor's data pointer is NULL) */
+    if (int r = launch_uv_taylor_packed(net, precision, packed, xyz, N, uvs, grad_uvs, (hipStream_t)stream)) return fail("uv_taylor", (hipError_t)r);
     return 0;
 }
 
 size_t texgs_uv_backward_temp_bytes(int32_t N) { return uv_backward_temp_bytes(N < 0 ? 0 : N); }
 
-static int uv_backward_impl(const TexGSUVNet* net, const float* xyz, const float* g_uvs, int32_t N, const TexGSUVNetGrad* out, void* temp,
-                            int mixed, void* stream) {
+int texgs_uv_backward(const TexGSUVNet* net, int32_t precision, const float* xyz, const float* g_uvs, int32_t N, const TexGSUVNetGrad* out,
+                      void* temp, void* stream) {
     if (!net || !out || !temp) return fail_msg("NULL argument");
-    if (int r = check_uvnet(net)) return r;
+    if (int r = check_uvnet(net, precision)) return r;
     if (N < 0) return fail_msg("N < 0");
     if (N > 0 && (!xyz || !g_uvs)) return fail_msg("NULL argument");
-    if (int r = launch_uv_backward(net, xyz, g_uvs, N, out, temp, mixed, (hipStream_t)stream)) return fail("uv_backward", (hipError_t)r);
+    if (int r = launch_uv_backward(net, xyz, g_uvs, N, out, temp, precision != TEXGS_UV_FP32, (hipStream_t)stream))
+        return fail("uv_backward", (hipError_t)r);
     return 0;
-}
-int texgs_uv_backward(const TexGSUVNet* net, const float* xyz, const float* g_uvs, int32_t N, const TexGSUVNetGrad* out, void* temp,
-                      void* stream) {
-    return uv_backward_impl(net, xyz, g_uvs, N, out, temp, 0, stream);
-}
-int texgs_uv_backward_mixed(const TexGSUVNet* net, const float* xyz, const float* g_uvs, int32_t N, const TexGSUVNetGrad* out, void* temp,
-                            void* stream) {
-    return uv_backward_impl(net, xyz, g_uvs, N, out, temp, 1, stream);
 }
 
 static int check_hashgrid(const TexGSHashGrid* g, uint32_t* n_params) {

@@ -82,15 +82,13 @@ int launch_geom_losses(const float* norm, const float* gt_norm, const float* gt_
                        float lambda_depth, float* sums, float* d_norm, float* d_depth, hipStream_t s);
 int launch_norm_from_depth(const float* depth, const float* viewmatrix, float tanfovx, float tanfovy, int H, int W, float threshold,
                            float* out_norm, float* out_mask, hipStream_t s);
-size_t uv_taylor_temp_bytes();
-int launch_uv_pack(const TexGSUVNet* net, void* packed, hipStream_t s);
-int launch_uv_taylor_packed(const TexGSUVNet* net, const void* packed, const float* xyz, int N, float* uvs, float* grad_uvs, hipStream_t s);
-int launch_uv_taylor(const TexGSUVNet* net, const float* xyz, int N, float* uvs, float* grad_uvs, void* temp, hipStream_t s);
-int launch_uv_pack_bf16x3(const TexGSUVNet* net, void* packed, hipStream_t s);
+size_t uv_packed_bytes(int precision);          // precision: TEXGS_UV_FP32 / _BF16X3 / _MIXED, validated by the caller
+int launch_uv_pack(const TexGSUVNet* net, int precision, void* packed, hipStream_t s);
+int launch_uv_taylor_packed(const TexGSUVNet* net, int precision, const void* packed, const float* xyz, int N, float* uvs, float* grad_uvs,
+                            hipStream_t s);
 size_t uv_backward_temp_bytes(int N);
 int launch_uv_backward(const TexGSUVNet* net, const float* xyz, const float* g, int N, const TexGSUVNetGrad* out, void* temp, int mixed,
                        hipStream_t s);
-int launch_uv_taylor_packed_bf16x3(const TexGSUVNet* net, const void* packed, const float* xyz, int N, float* uvs, float* grad_uvs, hipStream_t s);
 int hashgrid_levels(const TexGSHashGrid* g, float* scale, uint32_t* res, uint32_t* size, uint32_t* offset, uint32_t* n_params);
 int launch_hashgrid_forward(const TexGSHashGrid* g, const float* params, const float* x, int N, float* enc, hipStream_t s);
 size_t hashgrid_backward_temp_bytes(const TexGSHashGrid* g, int N);

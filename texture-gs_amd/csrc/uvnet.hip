@@ -9,34 +9,64 @@
 //     o  = W5 h3 + b5;  uv = o / max(|o|, 1e-12)        128 -> 3, F.normalize
 // Jacobian by FORWARD mode: the three tangents d/dx_j ride along as three more columns per point, so every 128x128
 // layer is one GEMM  Y[128 x 4P] = W[128 x 128] X[128 x 4P]  (value | d/dx0 | d/dx1 | d/dx2), ReLU masks taken from the value
-// column.  This is the one dense contraction next to the hot path, so it runs on the matrix cores: fp32-in / fp32-accumulate
-// v_mfma_f32_32x32x2_f32 (exact f32; a bf16 MFMA would put 1e-2 into J).  One workgroup = 32 points = a 128 x 128
-// activation tile in LDS; wave w owns rows [32w, 32w+32) of every layer: its 32 x 128 slice of W stays in 64 VGPRs
-// (pre-packed in MFMA A-operand order by k_uv_pack, so the loads are coalesced), the four 32x32 accumulators
-// (value, three tangents) in 64 more.  3 layers x 4 tiles x 64 k-steps = 768 MFMAs per wave, 64 cycles each.
+// column.  This is the one dense contraction next to the hot path, so it runs on the matrix cores.  One workgroup = 32 points =
+// a 128 x 128 activation tile in LDS; wave w owns rows [32w, 32w+32) of every layer and holds its slice of W in registers
+// (pre-packed in MFMA A-operand order by k_uv_pack / k_uv_pack_bf16x3, so the loads are coalesced).
+//
+// ONE forward body, uv_taylor_body<NF>, in three precisions.  The four columns of a point are PLANES 0 = value, 1..3 = tangents;
+// the first NF planes are kept in f32, the other 4 - NF as split bf16:
+//   * an f32 plane runs on v_mfma_f32_32x32x2_f32 (exact f32 products; a plain bf16 MFMA would put 1e-2 into J): the wave's
+//     32 x 128 slice of W in 64 VGPRs, 64 k-steps of 64 cycles per plane and layer;
+//   * a split-bf16 plane runs at the bf16 matrix-core rate (16x the f32-input rate on gfx950) at near-f32 accuracy: every operand
+//     is split x = hi + lo into two bf16 (8 + 8 significand bits) and a product is taken as  Wh Xh + Wh Xl + Wl Xh  -- three
+//     v_mfma_f32_32x32x16_bf16 with f32 accumulation; the dropped Wl Xl term and the residual of the split are ~2^-17 relative.
+//     - the activations live in LDS ALREADY SPLIT and k-contiguous, h / l[column][neuron] (bf16): a B operand (8 consecutive k of
+//       one column) is one 16-byte read; the epilogue of a layer converts each output once and writes four neurons (8 bytes) at a time;
+//     - rows are padded to 272 bytes: the 32 lanes of a half-wave start 17 x 16 bytes apart -> conflict-free 16-byte reads;
+//     - which k the hardware assigns to (lane >> 5, element j) does not matter: A and B are loaded with the SAME assignment
+//       (k = 16 s + 8 (lane >> 5) + j), and the instruction pairs equal (lane >> 5, j) of A and B.
+//   NF = 4  k_uv_taylor         all f32 (what the float64 parity tests check): 3 layers x 4 planes x 64 k-steps = 768 MFMAs per wave.
+//   NF = 1  k_uv_taylor_mixed   (the default) VALUE in f32, TANGENTS in split bf16.  The value column decides everything discrete --
+//           the ReLU masks, and through uvs the texel a pixel samples -- and it is the NF = 4 kernel's value column: the same helpers
+//           with the same operands in the same order, so the same masks and the same uvs bit for bit.  The three tangent columns
+//           only ever multiply pixel offsets of a few pixels, where 1e-5 relative is two orders below the operator's tolerance, and
+//           they are 3/4 of the work.  MFMA cycles per wave and layer: 64 x 64 (value) + 72 x 32 (tangents) = 6 400 against 16 384.
+//   NF = 0  k_uv_taylor_bf16x3  all split bf16: the masks then come from the split value column (inference only).
 #include "common.h"
 
 namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
 constexpr int UV_H = 128;          // hidden width
 constexpr int UV_P = 32;           // points per workgroup
+constexpr int UV_PITCH = 136;      // bf16 per activation row: 128 neurons + 8 pad (272 bytes)
 
-struct UVArgs {
+// The network's small tensors as every kernel of this file takes them (uv_net_ptrs fills them from a TexGSUVNet)
+struct UVNetPtrs {
     const float *W1, *b1, *b2, *emb, *b3, *b4, *W5, *b5, *off, *scale;
-    const float* packed;           // [3 layers][4 bands][64 steps][64 lanes]
+};
+struct UVArgs : UVNetPtrs {
+    const float* packed_f32;       // k_uv_pack: [3 layers][4 bands][64 steps][64 lanes]                                   (NF > 0)
+    const uint4* packed_b16;       // k_uv_pack_bf16x3: [3 layers][4 bands][8 k-steps][2: hi, lo][64 lanes] x 8 bf16      (NF < 4)
 };
 
-// The thin first layer, written with explicit roundings: every kernel of this file (f32, split-bf16, mixed, backward) forms the SAME
-// f32 pre-activation from the same inputs, whatever the compiler would have contracted -- so the f32-MFMA value columns of the f32
-// kernel, of the mixed kernel and of the backward's recomputation agree bit for bit, and with them the ReLU masks.
+// The thin first layer and every later multiply-add outside the MFMAs, written with explicit roundings: every kernel of this file
+// (the three forward precisions, the backward's recomputation) forms the SAME f32 values from the same inputs, whatever the compiler
+// would have contracted.
 __device__ __forceinline__ float uv_norm_in(float x, float off, float inv) { return __fmul_rn(__fsub_rn(x, off), inv); }
 __device__ __forceinline__ float uv_layer1_pre(float w0, float w1, float w2, float b, float x0, float x1, float x2) {
     return __fmaf_rn(w2, x2, __fmaf_rn(w1, x1, __fmaf_rn(w0, x0, b)));
 }
-// (bias, then the embedding: the order the f32 kernel's epilogue has always used)
+// (bias, then the embedding)
 __device__ __forceinline__ float uv_bias_emb(float acc, float bias, float emb) { return __fadd_rn(__fadd_rn(acc, bias), emb); }
+
+__device__ __forceinline__ void split_bf16(float x, __bf16& hi, __bf16& lo) {
+    hi = (__bf16)x;
+    lo = (__bf16)(x - (float)hi);
+}
 
 // W (row-major [128][128]) -> A-operand order of mfma_f32_32x32x2f32: lane l of band b at step s holds W[32b + (l & 31)][2s + (l >> 5)]
 __global__ void __launch_bounds__(256)
@@ -46,110 +76,6 @@ k_uv_pack(const float* __restrict__ W2, const float* __restrict__ W3, const floa
     const int lane = idx & 63, s = (idx >> 6) & 63, band = (idx >> 12) & 3, layer = idx >> 14;
     const float* W = layer == 0 ? W2 : (layer == 1 ? W3 : W4);
     packed[idx] = W[(band * 32 + (lane & 31)) * UV_H + 2 * s + (lane >> 5)];
-}
-
-__global__ void __launch_bounds__(256, 2)
-k_uv_taylor(UVArgs a, const float* __restrict__ xyz, int N, float* __restrict__ uvs, float* __restrict__ J) {
-    __shared__ float sX[UV_H][4 * UV_P];          // activations: row = neuron, col = plane * 32 + point (plane 0 = value)
-    __shared__ float sO[3][4 * UV_P];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int p0 = blockIdx.x * UV_P;
-    // ---- layer 1 (3 -> 128) on the VALU, with the optional input normalisation (uv_net.py:22-25)
-    for (int e = tid; e < UV_H * UV_P; e += 256) {
-        const int i = e >> 5, p = e & 31, n = min(p0 + p, N - 1);
-        float x[3], inv[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            inv[c] = a.scale ? 1.0f / a.scale[c] : 1.0f;
-            x[c] = uv_norm_in(xyz[3 * n + c], a.off ? a.off[c] : 0.0f, inv[c]);
-        }
-        const float w0 = a.W1[3 * i], w1 = a.W1[3 * i + 1], w2 = a.W1[3 * i + 2];
-        const float pre = uv_layer1_pre(w0, w1, w2, a.b1 ? a.b1[i] : 0.0f, x[0], x[1], x[2]);
-        const bool on = pre > 0.0f;
-        sX[i][p] = on ? pre : 0.0f;
-        sX[i][UV_P + p] = on ? w0 * inv[0] : 0.0f;
-        sX[i][2 * UV_P + p] = on ? w1 * inv[1] : 0.0f;
-        sX[i][3 * UV_P + p] = on ? w2 * inv[2] : 0.0f;
-    }
-    __syncthreads();
-    // ---- three 128 x 128 layers on the matrix cores
-    const int bn = lane & 31, bk = lane >> 5;
-    for (int layer = 0; layer < 3; ++layer) {
-        float areg[64];
-        const float* __restrict__ pk = a.packed + ((size_t)(layer * 4 + wave) * 64) * 64 + lane;
-#pragma unroll
-        for (int s = 0; s < 64; ++s) areg[s] = pk[s * 64];
-        f32x16 acc0 = {0.f}, acc1 = {0.f}, acc2 = {0.f}, acc3 = {0.f};
-#pragma unroll
-        for (int s = 0; s < 64; ++s) {
-            const float* row = &sX[2 * s + bk][bn];
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(areg[s], row[0], acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(areg[s], row[UV_P], acc1, 0, 0, 0);
-            acc2 = __builtin_amdgcn_mfma_f32_32x32x2f32(areg[s], row[2 * UV_P], acc2, 0, 0, 0);
-            acc3 = __builtin_amdgcn_mfma_f32_32x32x2f32(areg[s], row[3 * UV_P], acc3, 0, 0, 0);
-        }
-        __syncthreads();                           // every wave has read the layer's input
-        const float* bias = layer == 0 ? a.b2 : (layer == 1 ? a.b3 : a.b4);
-#pragma unroll
-        for (int v = 0; v < 16; ++v) {
-            const int i = wave * 32 + (v & 3) + 8 * (v >> 2) + 4 * bk;          // C/D layout: col = lane & 31
-            const float val = uv_bias_emb(acc0[v], bias ? bias[i] : 0.0f, layer == 0 ? a.emb[i] : 0.0f);
-            const bool on = val > 0.0f;
-            sX[i][bn] = on ? val : 0.0f;
-            sX[i][UV_P + bn] = on ? acc1[v] : 0.0f;
-            sX[i][2 * UV_P + bn] = on ? acc2[v] : 0.0f;
-            sX[i][3 * UV_P + bn] = on ? acc3[v] : 0.0f;
-        }
-        __syncthreads();
-    }
-    // ---- output layer (128 -> 3) for the value and the three tangents
-    for (int e = tid; e < 3 * 4 * UV_P; e += 256) {
-        const int c = e >> 7, col = e & 127;
-        float o = (col < UV_P && a.b5) ? a.b5[c] : 0.0f;
-        for (int i = 0; i < UV_H; ++i) o += a.W5[c * UV_H + i] * sX[i][col];
-        sO[c][col] = o;
-    }
-    __syncthreads();
-    if (tid < UV_P && p0 + tid < N) {
-        const int p = tid, n = p0 + p;
-        const float o0 = sO[0][p], o1 = sO[1][p], o2 = sO[2][p];
-        const float rn = 1.0f / fmaxf(sqrtf(o0 * o0 + o1 * o1 + o2 * o2), 1e-12f);
-        const float u0 = o0 * rn, u1 = o1 * rn, u2 = o2 * rn;
-        uvs[3 * n] = u0; uvs[3 * n + 1] = u1; uvs[3 * n + 2] = u2;
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {                 // d(o/|o|) = (I - u u^T) do / |o|;  J[n][3i + j] = d uv_i / d x_j
-            const float d0 = sO[0][(j + 1) * UV_P + p], d1 = sO[1][(j + 1) * UV_P + p], d2 = sO[2][(j + 1) * UV_P + p];
-            const float ud = u0 * d0 + u1 * d1 + u2 * d2;
-            J[9 * n + j] = (d0 - u0 * ud) * rn;
-            J[9 * n + 3 + j] = (d1 - u1 * ud) * rn;
-            J[9 * n + 6 + j] = (d2 - u2 * ud) * rn;
-        }
-    }
-}
-
-
-// ------------------------------------------------------------------------------------------------ split-bf16 variant (round 5)
-// The same network on the bf16 matrix-core rate (16x the f32-input MFMA rate on gfx950) at near-f32 accuracy: every operand is
-// split x = hi + lo into two bf16 (8 + 8 significand bits) and a product is taken as  Wh Xh + Wh Xl + Wl Xh  -- three
-// v_mfma_f32_32x32x16_bf16 with f32 accumulation; the dropped Wl Xl term and the residual of the split are ~2^-17 relative.
-// Opt-in (TexGSUVNet callers pick texgs_uv_taylor_packed_bf16x3): the f32 kernel above stays the checked default.
-//   * activations live in LDS ALREADY SPLIT and k-contiguous, sH / sL[column][neuron] (bf16): a B operand (8 consecutive k of one
-//     column) is one 16-byte read; the epilogue of a layer converts each output once and writes four neurons (8 bytes) at a time;
-//   * rows are padded to 272 bytes: the 32 lanes of a half-wave start 17 x 16 bytes apart -> conflict-free 16-byte reads;
-//   * which k the hardware assigns to (lane >> 5, element j) does not matter: A and B are loaded with the SAME assignment
-//     (k = 16 s + 8 (lane >> 5) + j), and the instruction pairs equal (lane >> 5, j) of A and B.
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-constexpr int UV_PITCH = 136;      // bf16 per activation row: 128 neurons + 8 pad (272 bytes)
-
-struct UVArgsB {
-    const float *W1, *b1, *b2, *emb, *b3, *b4, *W5, *b5, *off, *scale;
-    const uint4* packed;           // [3 layers][4 bands][8 k-steps][2: hi, lo][64 lanes] x 8 bf16
-};
-
-__device__ __forceinline__ void split_bf16(float x, __bf16& hi, __bf16& lo) {
-    hi = (__bf16)x;
-    lo = (__bf16)(x - (float)hi);
 }
 
 // W (row-major [128][128]) -> A-operand order of mfma_f32_32x32x16_bf16, split: lane l of band b at k-step s holds
@@ -169,240 +95,217 @@ k_uv_pack_bf16x3(const float* __restrict__ W2, const float* __restrict__ W3, con
     o[64] = __builtin_bit_cast(uint4, l);
 }
 
-__global__ void __launch_bounds__(256, 2)
-k_uv_taylor_bf16x3(UVArgsB a, const float* __restrict__ xyz, int N, float* __restrict__ uvs, float* __restrict__ J) {
-    __shared__ __attribute__((aligned(16))) __bf16 sH[4 * UV_P][UV_PITCH];     // activations, high halves: [column = plane * 32 + point][neuron]
-    __shared__ __attribute__((aligned(16))) __bf16 sL[4 * UV_P][UV_PITCH];     // low halves
-    __shared__ float sO[3][4 * UV_P];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int p0 = blockIdx.x * UV_P;
-    auto put = [&](int col, int i, float v) { __bf16 h, l; split_bf16(v, h, l); sH[col][i] = h; sL[col][i] = l; };
-    // ---- layer 1 (3 -> 128) on the VALU, with the optional input normalisation (uv_net.py:22-25)
-    for (int e = tid; e < UV_H * UV_P; e += 256) {
-        const int p = e >> 7, i = e & 127, n = min(p0 + p, N - 1);        // (neuron fastest: consecutive lanes write consecutive bf16)
-        float x[3], inv[3];
+// LDS of a forward workgroup: NF f32 planes x[neuron][plane * 32 + point], 4 - NF split planes h / l[plane * 32 + point][neuron],
+// the output layer's sums o[component][plane * 32 + point].  (A part that a precision does not have is an empty base.)
+template <int NP> struct UVPlanesF32 { float x[UV_H][NP * UV_P]; };
+template <> struct UVPlanesF32<0> {};
+template <int NP> struct alignas(16) UVPlanesB16 { __bf16 h[NP * UV_P][UV_PITCH], l[NP * UV_P][UV_PITCH]; };
+template <> struct UVPlanesB16<0> {};
+template <int NF> struct UVSmem : UVPlanesF32<NF>, UVPlanesB16<4 - NF> { float o[3][4 * UV_P]; };
+static_assert(sizeof(UVSmem<4>) == 67072 && sizeof(UVSmem<1>) == 70144 && sizeof(UVSmem<0>) == 71168, "LDS per workgroup");
+
+// ---- layer 1 (3 -> 128) on the VALU, with the optional input normalisation (uv_net.py:22-25): the four planes of neuron i at point n
+__device__ __forceinline__ void uv_layer1(const UVNetPtrs& a, const float* __restrict__ xyz, int n, int i, float (&v)[4]) {
+    float x[3], w[3];
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            inv[c] = a.scale ? 1.0f / a.scale[c] : 1.0f;
-            x[c] = uv_norm_in(xyz[3 * n + c], a.off ? a.off[c] : 0.0f, inv[c]);
-        }
-        const float w0 = a.W1[3 * i], w1 = a.W1[3 * i + 1], w2 = a.W1[3 * i + 2];
-        const float pre = uv_layer1_pre(w0, w1, w2, a.b1 ? a.b1[i] : 0.0f, x[0], x[1], x[2]);
-        const bool on = pre > 0.0f;
-        put(p, i, on ? pre : 0.0f);
-        put(UV_P + p, i, on ? w0 * inv[0] : 0.0f);
-        put(2 * UV_P + p, i, on ? w1 * inv[1] : 0.0f);
-        put(3 * UV_P + p, i, on ? w2 * inv[2] : 0.0f);
+    for (int c = 0; c < 3; ++c) {
+        const float inv = a.scale ? 1.0f / a.scale[c] : 1.0f;
+        x[c] = uv_norm_in(xyz[3 * n + c], a.off ? a.off[c] : 0.0f, inv);
+        w[c] = a.W1[3 * i + c];
+        v[1 + c] = __fmul_rn(w[c], inv);
     }
-    __syncthreads();
-    // ---- three 128 x 128 layers on the matrix cores, three bf16 products per f32 product
-    const int bn = lane & 31, bk = lane >> 5;
-    for (int layer = 0; layer < 3; ++layer) {
-        bf16x8 ah[8], al[8];
-        const uint4* __restrict__ pk = a.packed + ((size_t)((layer * 4 + wave) * 8) * 2) * 64 + lane;
+    v[0] = uv_layer1_pre(w[0], w[1], w[2], a.b1 ? a.b1[i] : 0.0f, x[0], x[1], x[2]);
+    if (!(v[0] > 0.0f)) v[0] = v[1] = v[2] = v[3] = 0.0f;
+}
+
+// ---- a 128 x 128 layer on the matrix cores.  Planes [0, NF): f32-input MFMA, the NF accumulators independent within a k-step
+template <int NF>
+__device__ __forceinline__ void uv_gemm_f32(const float* __restrict__ pk, const float (*sx)[NF * UV_P], int bn, int bk, f32x16 (&acc)[4]) {
+    float areg[64];
 #pragma unroll
-        for (int s = 0; s < 8; ++s) { ah[s] = __builtin_bit_cast(bf16x8, pk[(2 * s) * 64]); al[s] = __builtin_bit_cast(bf16x8, pk[(2 * s + 1) * 64]); }
-        f32x16 acc[4];
+    for (int s = 0; s < 64; ++s) areg[s] = pk[s * 64];
 #pragma unroll
-        for (int t = 0; t < 4; ++t) acc[t] = f32x16{0.f};
+    for (int s = 0; s < 64; ++s) {
+        const float* row = &sx[2 * s + bk][bn];
 #pragma unroll
-        for (int s = 0; s < 8; ++s) {
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                const bf16x8 bh = *reinterpret_cast<const bf16x8*>(&sH[t * UV_P + bn][16 * s + 8 * bk]);
-                const bf16x8 bl = *reinterpret_cast<const bf16x8*>(&sL[t * UV_P + bn][16 * s + 8 * bk]);
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[s], bh, acc[t], 0, 0, 0);
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[s], bl, acc[t], 0, 0, 0);
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[s], bh, acc[t], 0, 0, 0);
-            }
-        }
-        __syncthreads();                           // every wave has read the layer's input
-        const float* bias = layer == 0 ? a.b2 : (layer == 1 ? a.b3 : a.b4);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {              // C/D layout: col = lane & 31, rows (v & 3) + 8 (v >> 2) + 4 (lane >> 5): four consecutive per q
-            const int i0 = wave * 32 + 8 * q + 4 * bk;
-            bool on[4];
-            bf16x4 h, l;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float val = uv_bias_emb(acc[0][4 * q + r], bias ? bias[i0 + r] : 0.0f, layer == 0 ? a.emb[i0 + r] : 0.0f);
-                on[r] = val > 0.0f;
-                __bf16 x, y; split_bf16(on[r] ? val : 0.0f, x, y); h[r] = x; l[r] = y;
-            }
-            *reinterpret_cast<bf16x4*>(&sH[bn][i0]) = h; *reinterpret_cast<bf16x4*>(&sL[bn][i0]) = l;
-#pragma unroll
-            for (int t = 1; t < 4; ++t) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) { __bf16 x, y; split_bf16(on[r] ? acc[t][4 * q + r] : 0.0f, x, y); h[r] = x; l[r] = y; }
-                *reinterpret_cast<bf16x4*>(&sH[t * UV_P + bn][i0]) = h; *reinterpret_cast<bf16x4*>(&sL[t * UV_P + bn][i0]) = l;
-            }
-        }
-        __syncthreads();
+        for (int t = 0; t < NF; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(areg[s], row[t * UV_P], acc[t], 0, 0, 0);
     }
-    // ---- output layer (128 -> 3) for the value and the three tangents, f32 on the re-joined halves
-    for (int e = tid; e < 3 * 4 * UV_P; e += 256) {
-        const int c = e >> 7, col = e & 127;
-        float o = (col < UV_P && a.b5) ? a.b5[c] : 0.0f;
-        for (int i = 0; i < UV_H; i += 8) {
-            const bf16x8 h = *reinterpret_cast<const bf16x8*>(&sH[col][i]), l = *reinterpret_cast<const bf16x8*>(&sL[col][i]);
+}
+// Planes [NF, 4): three bf16 products per f32 product, Ah Bh + Ah Bl + Al Bh
+template <int NF>
+__device__ __forceinline__ void uv_gemm_b16(const uint4* __restrict__ pk, const __bf16 (*sh)[UV_PITCH], const __bf16 (*sl)[UV_PITCH], int bn, int bk,
+                                            f32x16 (&acc)[4]) {
+    bf16x8 ah[8], al[8];
 #pragma unroll
-            for (int j = 0; j < 8; ++j) o += a.W5[c * UV_H + i + j] * ((float)h[j] + (float)l[j]);
-        }
-        sO[c][col] = o;
-    }
-    __syncthreads();
-    if (tid < UV_P && p0 + tid < N) {
-        const int p = tid, n = p0 + p;
-        const float o0 = sO[0][p], o1 = sO[1][p], o2 = sO[2][p];
-        const float rn = 1.0f / fmaxf(sqrtf(o0 * o0 + o1 * o1 + o2 * o2), 1e-12f);
-        const float u0 = o0 * rn, u1 = o1 * rn, u2 = o2 * rn;
-        uvs[3 * n] = u0; uvs[3 * n + 1] = u1; uvs[3 * n + 2] = u2;
+    for (int s = 0; s < 8; ++s) { ah[s] = __builtin_bit_cast(bf16x8, pk[(2 * s) * 64]); al[s] = __builtin_bit_cast(bf16x8, pk[(2 * s + 1) * 64]); }
 #pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            const float d0 = sO[0][(j + 1) * UV_P + p], d1 = sO[1][(j + 1) * UV_P + p], d2 = sO[2][(j + 1) * UV_P + p];
-            const float ud = u0 * d0 + u1 * d1 + u2 * d2;
-            J[9 * n + j] = (d0 - u0 * ud) * rn;
-            J[9 * n + 3 + j] = (d1 - u1 * ud) * rn;
-            J[9 * n + 6 + j] = (d2 - u2 * ud) * rn;
+    for (int s = 0; s < 8; ++s) {
+#pragma unroll
+        for (int t = 0; t < 4 - NF; ++t) {
+            const bf16x8 bh = *reinterpret_cast<const bf16x8*>(&sh[t * UV_P + bn][16 * s + 8 * bk]);
+            const bf16x8 bl = *reinterpret_cast<const bf16x8*>(&sl[t * UV_P + bn][16 * s + 8 * bk]);
+            acc[NF + t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[s], bh, acc[NF + t], 0, 0, 0);
+            acc[NF + t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[s], bl, acc[NF + t], 0, 0, 0);
+            acc[NF + t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[s], bh, acc[NF + t], 0, 0, 0);
         }
     }
 }
 
+// ---- a layer's epilogue: bias (+ embedding), the ReLU mask from plane 0, write-back as the next layer's input.
+// C/D layout: col = lane & 31, element v = 4 q + r is row 8 q + 4 (lane >> 5) + r of the wave's 32: four consecutive neurons per q
+template <int NF>
+__device__ __forceinline__ void uv_epilogue(UVSmem<NF>& sm, const float* __restrict__ bias, const float* __restrict__ emb, int wave, int bn, int bk,
+                                            const f32x16 (&acc)[4]) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int i0 = wave * 32 + 8 * q + 4 * bk;
+        float val[4];
+        bool on[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float pre = uv_bias_emb(acc[0][4 * q + r], bias ? bias[i0 + r] : 0.0f, emb ? emb[i0 + r] : 0.0f);
+            on[r] = pre > 0.0f;
+            val[r] = on[r] ? pre : 0.0f;
+            if constexpr (NF > 0) {
+                sm.x[i0 + r][bn] = val[r];
+#pragma unroll
+                for (int t = 1; t < NF; ++t) sm.x[i0 + r][t * UV_P + bn] = on[r] ? acc[t][4 * q + r] : 0.0f;
+            }
+        }
+        if constexpr (NF < 4) {
+#pragma unroll
+            for (int t = NF; t < 4; ++t) {
+                bf16x4 h, l;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    __bf16 x, y;
+                    split_bf16(t == 0 ? val[r] : (on[r] ? acc[t][4 * q + r] : 0.0f), x, y);
+                    h[r] = x; l[r] = y;
+                }
+                *reinterpret_cast<bf16x4*>(&sm.h[(t - NF) * UV_P + bn][i0]) = h;
+                *reinterpret_cast<bf16x4*>(&sm.l[(t - NF) * UV_P + bn][i0]) = l;
+            }
+        }
+    }
+}
 
-// ------------------------------------------------------------------------------------------------ mixed variant (round 5)
-// VALUE in f32, TANGENTS in split bf16.  The value column decides everything discrete -- the ReLU masks, and through uvs the
-// texel a pixel samples -- so it stays on the f32-input MFMA exactly as in k_uv_taylor (same masks, same uvs to the last bit of
-// the accumulation order); the three tangent columns only ever multiply pixel offsets of a few pixels, where 1e-5 relative is two
-// orders below the operator's tolerance, and they are 3/4 of the work: they take the three-product bf16 path of
-// k_uv_taylor_bf16x3.  MFMA cycles per wave and layer: 64 x 64 (value) + 72 x 32 (tangents) = 6 400 against 16 384 all-f32.
-struct UVArgsM {
-    const float *W1, *b1, *b2, *emb, *b3, *b4, *W5, *b5, *off, *scale;
-    const float* packed_f32;       // k_uv_pack layout
-    const uint4* packed_b16;       // k_uv_pack_bf16x3 layout
-};
+// ---- output layer (128 -> 3), one column: o + sum_i w[i] h[i], i ascending.  f32 plane: col = &x[0][column], rows `pitch` apart
+__device__ __forceinline__ float uv_out_f32(const float* __restrict__ w, const float* col, int pitch, float o) {
+    for (int i = 0; i < UV_H; ++i) o = __fmaf_rn(w[i], col[i * pitch], o);
+    return o;
+}
+// split plane: f32 on the re-joined halves.  Terms 0..115 are fused, terms 116..127 a rounded product then a rounded add: what the
+// vectoriser made of the tail of this sum in the split kernels since they exist (an accident, frozen like uv_finish's orders below
+// because J -- and bf16x3's uvs -- are pinned to those bits).
+template <int FUSED>      // eight terms from i on, the first FUSED of them fused
+__device__ __forceinline__ float uv_out_b16_x8(const float* __restrict__ w, const __bf16* sh, const __bf16* sl, int i, float o) {
+    const bf16x8 h = *reinterpret_cast<const bf16x8*>(sh + i), l = *reinterpret_cast<const bf16x8*>(sl + i);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const float x = __fadd_rn((float)h[j], (float)l[j]);
+        o = j < FUSED ? __fmaf_rn(w[i + j], x, o) : __fadd_rn(o, __fmul_rn(x, w[i + j]));
+    }
+    return o;
+}
+__device__ __forceinline__ float uv_out_b16(const float* __restrict__ w, const __bf16* sh, const __bf16* sl, float o) {
+    for (int i = 0; i < UV_H - 16; i += 8) o = uv_out_b16_x8<8>(w, sh, sl, i, o);
+    o = uv_out_b16_x8<4>(w, sh, sl, UV_H - 16, o);
+    return uv_out_b16_x8<0>(w, sh, sl, UV_H - 8, o);
+}
 
-__global__ void __launch_bounds__(256, 2)
-k_uv_taylor_mixed(UVArgsM a, const float* __restrict__ xyz, int N, float* __restrict__ uvs, float* __restrict__ J) {
-    __shared__ float sV[UV_H][UV_P];                                            // value activations [neuron][point]
-    __shared__ __attribute__((aligned(16))) __bf16 sH[3 * UV_P][UV_PITCH];     // tangent activations, high halves [plane * 32 + point][neuron]
-    __shared__ __attribute__((aligned(16))) __bf16 sL[3 * UV_P][UV_PITCH];     // low halves
-    __shared__ float sO[3][4 * UV_P];
+// ---- F.normalize and its Jacobian for point p of the tile (global index n): d(o/|o|) = (I - u u^T) do / |o|;  J[n][3i + j] = d uv_i / d x_j.
+// No contraction is left to the compiler here.  The sums of three products are rounded in the orders these kernels have always been
+// compiled to -- |o|^2 and the three columns' u . d each in its own: an accident of vectorisation, frozen because the outputs are pinned
+// to those bits.
+__device__ __forceinline__ void uv_finish(const float (&sO)[3][4 * UV_P], int p, int n, float* __restrict__ uvs, float* __restrict__ J) {
+#pragma clang fp contract(off)
+    const float o0 = sO[0][p], o1 = sO[1][p], o2 = sO[2][p];
+    const float rn = 1.0f / fmaxf(sqrtf(__fmaf_rn(o1, o1, o0 * o0) + o2 * o2), 1e-12f);
+    const float u[3] = {o0 * rn, o1 * rn, o2 * rn};
+    uvs[3 * n] = u[0]; uvs[3 * n + 1] = u[1]; uvs[3 * n + 2] = u[2];
+    float d[3][3];                                    // d[i][j] = d o_i / d x_j
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) d[i][j] = sO[i][(j + 1) * UV_P + p];
+    const float ud[3] = {__fmaf_rn(u[2], d[2][0], __fmaf_rn(u[0], d[0][0], u[1] * d[1][0])),
+                         __fmaf_rn(u[2], d[2][1], __fmaf_rn(u[1], d[1][1], u[0] * d[0][1])),
+                         __fmaf_rn(u[2], d[2][2], u[0] * d[0][2] + u[1] * d[1][2])};
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) J[9 * n + 3 * i + j] = __fmaf_rn(-u[i], ud[j], d[i][j]) * rn;
+}
+
+template <int NF>
+__device__ __forceinline__ void uv_taylor_body(const UVArgs& a, const float* __restrict__ xyz, int N, float* __restrict__ uvs, float* __restrict__ J) {
+    __shared__ UVSmem<NF> sm;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int p0 = blockIdx.x * UV_P;
-    auto put = [&](int col, int i, float v) { __bf16 h, l; split_bf16(v, h, l); sH[col][i] = h; sL[col][i] = l; };
-    auto layer1 = [&](int i, int p, float& pre, float (&t)[3]) {
-        const int n = min(p0 + p, N - 1);
-        float x[3];
+    // ---- layer 1: point-fastest for the f32 planes, neuron-fastest for the split planes (each layout wants its own lane order: consecutive
+    // lanes write consecutive words; where both exist the recomputation is five FMAs).  Points past N repeat point N - 1.
+    if constexpr (NF > 0) {
+        for (int e = tid; e < UV_H * UV_P; e += 256) {
+            const int i = e >> 5, p = e & 31;
+            float v[4];
+            uv_layer1(a, xyz, min(p0 + p, N - 1), i, v);
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float inv = a.scale ? 1.0f / a.scale[c] : 1.0f;
-            x[c] = uv_norm_in(xyz[3 * n + c], a.off ? a.off[c] : 0.0f, inv);
-            t[c] = a.W1[3 * i + c] * inv;
+            for (int t = 0; t < NF; ++t) sm.x[i][t * UV_P + p] = v[t];
         }
-        pre = uv_layer1_pre(a.W1[3 * i], a.W1[3 * i + 1], a.W1[3 * i + 2], a.b1 ? a.b1[i] : 0.0f, x[0], x[1], x[2]);
-    };
-    // ---- layer 1 (3 -> 128) on the VALU, twice: point-fastest for the f32 plane, neuron-fastest for the bf16 planes (each
-    // layout wants its own lane order; the recomputation is five FMAs)
-    for (int e = tid; e < UV_H * UV_P; e += 256) {
-        const int i = e >> 5, p = e & 31;
-        float pre, t[3];
-        layer1(i, p, pre, t);
-        sV[i][p] = pre > 0.0f ? pre : 0.0f;
     }
-    for (int e = tid; e < UV_H * UV_P; e += 256) {
-        const int p = e >> 7, i = e & 127;
-        float pre, t[3];
-        layer1(i, p, pre, t);
-        const bool on = pre > 0.0f;
-        put(p, i, on ? t[0] : 0.0f); put(UV_P + p, i, on ? t[1] : 0.0f); put(2 * UV_P + p, i, on ? t[2] : 0.0f);
+    if constexpr (NF < 4) {
+        for (int e = tid; e < UV_H * UV_P; e += 256) {
+            const int p = e >> 7, i = e & 127;
+            float v[4];
+            uv_layer1(a, xyz, min(p0 + p, N - 1), i, v);
+#pragma unroll
+            for (int t = NF; t < 4; ++t) {
+                __bf16 h, l;
+                split_bf16(v[t], h, l);
+                sm.h[(t - NF) * UV_P + p][i] = h; sm.l[(t - NF) * UV_P + p][i] = l;
+            }
+        }
     }
     __syncthreads();
+    // ---- three 128 x 128 layers on the matrix cores
     const int bn = lane & 31, bk = lane >> 5;
     for (int layer = 0; layer < 3; ++layer) {
         f32x16 acc[4];
 #pragma unroll
         for (int t = 0; t < 4; ++t) acc[t] = f32x16{0.f};
-        {   // value: f32-input MFMA, as k_uv_taylor
-            float areg[64];
-            const float* __restrict__ pk = a.packed_f32 + ((size_t)(layer * 4 + wave) * 64) * 64 + lane;
-#pragma unroll
-            for (int s = 0; s < 64; ++s) areg[s] = pk[s * 64];
-#pragma unroll
-            for (int s = 0; s < 64; ++s) acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(areg[s], sV[2 * s + bk][bn], acc[0], 0, 0, 0);
-        }
-        {   // tangents: three bf16 products per f32 product, as k_uv_taylor_bf16x3
-            bf16x8 ah[8], al[8];
-            const uint4* __restrict__ pk = a.packed_b16 + ((size_t)((layer * 4 + wave) * 8) * 2) * 64 + lane;
-#pragma unroll
-            for (int s = 0; s < 8; ++s) { ah[s] = __builtin_bit_cast(bf16x8, pk[(2 * s) * 64]); al[s] = __builtin_bit_cast(bf16x8, pk[(2 * s + 1) * 64]); }
-#pragma unroll
-            for (int s = 0; s < 8; ++s) {
-#pragma unroll
-                for (int t = 0; t < 3; ++t) {
-                    const bf16x8 bh = *reinterpret_cast<const bf16x8*>(&sH[t * UV_P + bn][16 * s + 8 * bk]);
-                    const bf16x8 bl = *reinterpret_cast<const bf16x8*>(&sL[t * UV_P + bn][16 * s + 8 * bk]);
-                    acc[1 + t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[s], bh, acc[1 + t], 0, 0, 0);
-                    acc[1 + t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[s], bl, acc[1 + t], 0, 0, 0);
-                    acc[1 + t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[s], bh, acc[1 + t], 0, 0, 0);
-                }
-            }
-        }
+        if constexpr (NF > 0) uv_gemm_f32<NF>(a.packed_f32 + ((size_t)(layer * 4 + wave) * 64) * 64 + lane, sm.x, bn, bk, acc);
+        if constexpr (NF < 4) uv_gemm_b16<NF>(a.packed_b16 + ((size_t)((layer * 4 + wave) * 8) * 2) * 64 + lane, sm.h, sm.l, bn, bk, acc);
         __syncthreads();                           // every wave has read the layer's input
-        const float* bias = layer == 0 ? a.b2 : (layer == 1 ? a.b3 : a.b4);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {              // C/D layout: col = lane & 31, rows (v & 3) + 8 (v >> 2) + 4 (lane >> 5): four consecutive per q
-            const int i0 = wave * 32 + 8 * q + 4 * bk;
-            bool on[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float val = uv_bias_emb(acc[0][4 * q + r], bias ? bias[i0 + r] : 0.0f, layer == 0 ? a.emb[i0 + r] : 0.0f);
-                on[r] = val > 0.0f;
-                sV[i0 + r][bn] = on[r] ? val : 0.0f;
-            }
-#pragma unroll
-            for (int t = 0; t < 3; ++t) {
-                bf16x4 h, l;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) { __bf16 x, y; split_bf16(on[r] ? acc[1 + t][4 * q + r] : 0.0f, x, y); h[r] = x; l[r] = y; }
-                *reinterpret_cast<bf16x4*>(&sH[t * UV_P + bn][i0]) = h; *reinterpret_cast<bf16x4*>(&sL[t * UV_P + bn][i0]) = l;
-            }
-        }
+        uv_epilogue<NF>(sm, layer == 0 ? a.b2 : (layer == 1 ? a.b3 : a.b4), layer == 0 ? a.emb : nullptr, wave, bn, bk, acc);
         __syncthreads();
     }
-    // ---- output layer (128 -> 3): the value column from the f32 plane, the tangents from the re-joined halves
+    // ---- output layer (128 -> 3) for the value and the three tangents
     for (int e = tid; e < 3 * 4 * UV_P; e += 256) {
         const int c = e >> 7, col = e & 127;
-        float o;
-        if (col < UV_P) {
-            o = a.b5 ? a.b5[c] : 0.0f;
-            for (int i = 0; i < UV_H; ++i) o += a.W5[c * UV_H + i] * sV[i][col];
+        float o = (col < UV_P && a.b5) ? a.b5[c] : 0.0f;
+        const float* __restrict__ w = a.W5 + c * UV_H;
+        if (col < NF * UV_P) {
+            if constexpr (NF > 0) o = uv_out_f32(w, &sm.x[0][col], NF * UV_P, o);
         } else {
-            o = 0.0f;
-            const int tc = col - UV_P;
-            for (int i = 0; i < UV_H; i += 8) {
-                const bf16x8 h = *reinterpret_cast<const bf16x8*>(&sH[tc][i]), l = *reinterpret_cast<const bf16x8*>(&sL[tc][i]);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) o += a.W5[c * UV_H + i + j] * ((float)h[j] + (float)l[j]);
-            }
+            if constexpr (NF < 4) o = uv_out_b16(w, sm.h[col - NF * UV_P], sm.l[col - NF * UV_P], o);
         }
-        sO[c][col] = o;
+        sm.o[c][col] = o;
     }
     __syncthreads();
-    if (tid < UV_P && p0 + tid < N) {
-        const int p = tid, n = p0 + p;
-        const float o0 = sO[0][p], o1 = sO[1][p], o2 = sO[2][p];
-        const float rn = 1.0f / fmaxf(sqrtf(o0 * o0 + o1 * o1 + o2 * o2), 1e-12f);
-        const float u0 = o0 * rn, u1 = o1 * rn, u2 = o2 * rn;
-        uvs[3 * n] = u0; uvs[3 * n + 1] = u1; uvs[3 * n + 2] = u2;
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            const float d0 = sO[0][(j + 1) * UV_P + p], d1 = sO[1][(j + 1) * UV_P + p], d2 = sO[2][(j + 1) * UV_P + p];
-            const float ud = u0 * d0 + u1 * d1 + u2 * d2;
-            J[9 * n + j] = (d0 - u0 * ud) * rn;
-            J[9 * n + 3 + j] = (d1 - u1 * ud) * rn;
-            J[9 * n + 6 + j] = (d2 - u2 * ud) * rn;
-        }
-    }
+    if (tid < UV_P && p0 + tid < N) uv_finish(sm.o, tid, p0 + tid, uvs, J);
+}
+
+__global__ void __launch_bounds__(256, 2)
+k_uv_taylor(UVArgs a, const float* __restrict__ xyz, int N, float* __restrict__ uvs, float* __restrict__ J) {
+    uv_taylor_body<4>(a, xyz, N, uvs, J);
+}
+__global__ void __launch_bounds__(256, 2)
+k_uv_taylor_bf16x3(UVArgs a, const float* __restrict__ xyz, int N, float* __restrict__ uvs, float* __restrict__ J) {
+    uv_taylor_body<0>(a, xyz, N, uvs, J);
+}
+__global__ void __launch_bounds__(256, 2)
+k_uv_taylor_mixed(UVArgs a, const float* __restrict__ xyz, int N, float* __restrict__ uvs, float* __restrict__ J) {
+    uv_taylor_body<1>(a, xyz, N, uvs, J);
 }
 
 // ------------------------------------------------------------------------------------------------ backward (round 5)
@@ -429,8 +332,7 @@ constexpr int BW_P = 64;             // points per tile
 constexpr int BW_PITCH = BW_P + 1;
 constexpr int BW_SMALL = 10;         // per-neuron vectors a thread accumulates: dW1[.][0..2], db1, db2, db3, db4, dW5[0..2][.]
 
-struct UVBwdArgs {
-    const float *W1, *b1, *b2, *emb, *b3, *b4, *W5, *b5, *off, *scale;
+struct UVBwdArgs : UVNetPtrs {
     const float4* pk4;               // A operands of W2, W3, W4, W2^T, W3^T, W4^T (k_uv_pack_bwd)
     const float* xyz;
     const float* g;
@@ -937,44 +839,48 @@ k_uv_backward_reduce(const float* __restrict__ partW, const float* __restrict__ 
 
 }  // namespace
 
-size_t uv_taylor_temp_bytes() { return (size_t)3 * UV_H * UV_H * sizeof(float); }
+static UVNetPtrs uv_net_ptrs(const TexGSUVNet* net) {
+    return {net->W1, net->b1, net->b2, net->emb, net->b3, net->b4, net->W5, net->b5, net->xyz_offset, net->xyz_scale};
+}
 
-// W2, W3, W4 -> MFMA A-operand order.  The result depends on the weights only: callers that evaluate the same network again
-// (every view of a retexture / viewer session; every step between two optimizer updates) pack once and reuse `packed`.
-int launch_uv_pack(const TexGSUVNet* net, void* packed, hipStream_t s) {
-    hipLaunchKernelGGL(k_uv_pack, dim3(3 * 4 * 64 * 64 / 256), dim3(256), 0, s, net->W2, net->W3, net->W4, reinterpret_cast<float*>(packed));
+// W2, W3, W4 in MFMA A-operand order.  One layout is 192 KB, f32 and split bf16 alike; TEXGS_UV_MIXED holds both, f32 first.
+// The result depends on the weights only: callers that evaluate the same network again (every view of a retexture / viewer
+// session; every step between two optimizer updates) pack once and reuse `packed`.
+constexpr size_t UV_PACK_BYTES = (size_t)3 * UV_H * UV_H * sizeof(float);
+
+size_t uv_packed_bytes(int precision) {
+    return precision == TEXGS_UV_MIXED ? 2 * UV_PACK_BYTES : (precision == TEXGS_UV_FP32 || precision == TEXGS_UV_BF16X3 ? UV_PACK_BYTES : 0);
+}
+
+// where the split-bf16 layout starts in `packed` (the f32 layout, where there is one, starts at 0)
+static size_t uv_packed_b16_offset(int precision) { return precision == TEXGS_UV_MIXED ? UV_PACK_BYTES : 0; }
+
+static UVArgs uv_args(const TexGSUVNet* net, int precision, const void* packed) {
+    const char* p = reinterpret_cast<const char*>(packed);
+    return {uv_net_ptrs(net), precision == TEXGS_UV_BF16X3 ? nullptr : reinterpret_cast<const float*>(p),
+            precision == TEXGS_UV_FP32 ? nullptr : reinterpret_cast<const uint4*>(p + uv_packed_b16_offset(precision))};
+}
+
+int launch_uv_pack(const TexGSUVNet* net, int precision, void* packed, hipStream_t s) {
+    char* p = reinterpret_cast<char*>(packed);
+    if (precision != TEXGS_UV_BF16X3) {
+        hipLaunchKernelGGL(k_uv_pack, dim3(3 * 4 * 64 * 64 / 256), dim3(256), 0, s, net->W2, net->W3, net->W4, reinterpret_cast<float*>(p));
+        if (hipError_t e = hipGetLastError()) return (int)e;
+    }
+    if (precision != TEXGS_UV_FP32)
+        hipLaunchKernelGGL(k_uv_pack_bf16x3, dim3(3 * 4 * 8 * 64 / 256), dim3(256), 0, s, net->W2, net->W3, net->W4,
+                           reinterpret_cast<uint4*>(p + uv_packed_b16_offset(precision)));
     return (int)hipGetLastError();
 }
 
-int launch_uv_taylor_packed(const TexGSUVNet* net, const void* packed, const float* xyz, int N, float* uvs, float* grad_uvs,
+int launch_uv_taylor_packed(const TexGSUVNet* net, int precision, const void* packed, const float* xyz, int N, float* uvs, float* grad_uvs,
                             hipStream_t s) {
     if (N <= 0) return 0;
-    UVArgs a;
-    a.W1 = net->W1; a.b1 = net->b1; a.b2 = net->b2; a.emb = net->emb; a.b3 = net->b3; a.b4 = net->b4; a.W5 = net->W5; a.b5 = net->b5;
-    a.off = net->xyz_offset; a.scale = net->xyz_scale; a.packed = reinterpret_cast<const float*>(packed);
-    hipLaunchKernelGGL(k_uv_taylor, dim3((N + UV_P - 1) / UV_P), dim3(256), 0, s, a, xyz, N, uvs, grad_uvs);
-    return (int)hipGetLastError();
-}
-
-int launch_uv_taylor(const TexGSUVNet* net, const float* xyz, int N, float* uvs, float* grad_uvs, void* temp, hipStream_t s) {
-    if (N <= 0) return 0;
-    if (int r = launch_uv_pack(net, temp, s)) return r;
-    return launch_uv_taylor_packed(net, temp, xyz, N, uvs, grad_uvs, s);
-}
-
-// split-bf16 variant: the same two steps (the packed buffer has the same size, a different layout)
-int launch_uv_pack_bf16x3(const TexGSUVNet* net, void* packed, hipStream_t s) {
-    hipLaunchKernelGGL(k_uv_pack_bf16x3, dim3(3 * 4 * 8 * 64 / 256), dim3(256), 0, s, net->W2, net->W3, net->W4, reinterpret_cast<uint4*>(packed));
-    return (int)hipGetLastError();
-}
-
-int launch_uv_taylor_packed_bf16x3(const TexGSUVNet* net, const void* packed, const float* xyz, int N, float* uvs, float* grad_uvs,
-                                   hipStream_t s) {
-    if (N <= 0) return 0;
-    UVArgsB a;
-    a.W1 = net->W1; a.b1 = net->b1; a.b2 = net->b2; a.emb = net->emb; a.b3 = net->b3; a.b4 = net->b4; a.W5 = net->W5; a.b5 = net->b5;
-    a.off = net->xyz_offset; a.scale = net->xyz_scale; a.packed = reinterpret_cast<const uint4*>(packed);
-    hipLaunchKernelGGL(k_uv_taylor_bf16x3, dim3((N + UV_P - 1) / UV_P), dim3(256), 0, s, a, xyz, N, uvs, grad_uvs);
+    const UVArgs a = uv_args(net, precision, packed);
+    const dim3 grid((N + UV_P - 1) / UV_P), block(256);
+    if (precision == TEXGS_UV_FP32) hipLaunchKernelGGL(k_uv_taylor, grid, block, 0, s, a, xyz, N, uvs, grad_uvs);
+    else if (precision == TEXGS_UV_BF16X3) hipLaunchKernelGGL(k_uv_taylor_bf16x3, grid, block, 0, s, a, xyz, N, uvs, grad_uvs);
+    else hipLaunchKernelGGL(k_uv_taylor_mixed, grid, block, 0, s, a, xyz, N, uvs, grad_uvs);
     return (int)hipGetLastError();
 }
 
@@ -982,7 +888,7 @@ int launch_uv_taylor_packed_bf16x3(const TexGSUVNet* net, const void* packed, co
 static int uv_backward_blocks(int N) { const int t = (N + BW_P - 1) / BW_P; return t < 256 ? (t < 1 ? 1 : t) : 256; }
 static size_t uv_backward_part_floats() { return (size_t)3 * UV_H * UV_H + 2 * BW_SMALL * UV_H + 4; }
 size_t uv_backward_temp_bytes(int N) {
-    return 2 * uv_taylor_temp_bytes() + (size_t)uv_backward_blocks(N) * uv_backward_part_floats() * sizeof(float);
+    return 2 * UV_PACK_BYTES + (size_t)uv_backward_blocks(N) * uv_backward_part_floats() * sizeof(float);
 }
 
 int launch_uv_backward(const TexGSUVNet* net, const float* xyz, const float* g, int N, const TexGSUVNetGrad* out, void* temp, int mixed,
@@ -1003,32 +909,11 @@ int launch_uv_backward(const TexGSUVNet* net, const float* xyz, const float* g, 
         } else {
             hipLaunchKernelGGL(k_uv_pack_bwd, dim3(6 * 4 * 64 * 64 / 256), dim3(256), 0, s, net->W2, net->W3, net->W4, packed, 6);
         }
-        UVBwdArgs a;
-        a.W1 = net->W1; a.b1 = net->b1; a.b2 = net->b2; a.emb = net->emb; a.b3 = net->b3; a.b4 = net->b4; a.W5 = net->W5; a.b5 = net->b5;
-        a.off = net->xyz_offset; a.scale = net->xyz_scale; a.pk4 = reinterpret_cast<const float4*>(packed); a.xyz = xyz; a.g = g;
-        a.N = N; a.n_tiles = (N + BW_P - 1) / BW_P; a.partW = partW; a.partS = partS; a.partB5 = partB5;
+        const UVBwdArgs a{uv_net_ptrs(net), reinterpret_cast<const float4*>(packed), xyz, g, N, (N + BW_P - 1) / BW_P, partW, partS, partB5};
         if (mixed) hipLaunchKernelGGL(k_uv_backward<true>, dim3(G), dim3(256), 0, s, a);
         else hipLaunchKernelGGL(k_uv_backward<false>, dim3(G), dim3(256), 0, s, a);
     }
     const int n_out = 3 * UV_H * UV_H + BW_SMALL * UV_H + 3;
     hipLaunchKernelGGL(k_uv_backward_reduce, dim3((n_out + 255) / 256), dim3(256), 0, s, partW, partS, partB5, G, o);
-    return (int)hipGetLastError();
-}
-
-// mixed variant: `packed` holds BOTH layouts back to back (2 x uv_taylor_temp_bytes(): f32 pack, then split-bf16 pack)
-int launch_uv_pack_mixed(const TexGSUVNet* net, void* packed, hipStream_t s) {
-    if (int r = launch_uv_pack(net, packed, s)) return r;
-    return launch_uv_pack_bf16x3(net, reinterpret_cast<char*>(packed) + uv_taylor_temp_bytes(), s);
-}
-
-int launch_uv_taylor_packed_mixed(const TexGSUVNet* net, const void* packed, const float* xyz, int N, float* uvs, float* grad_uvs,
-                                  hipStream_t s) {
-    if (N <= 0) return 0;
-    UVArgsM a;
-    a.W1 = net->W1; a.b1 = net->b1; a.b2 = net->b2; a.emb = net->emb; a.b3 = net->b3; a.b4 = net->b4; a.W5 = net->W5; a.b5 = net->b5;
-    a.off = net->xyz_offset; a.scale = net->xyz_scale;
-    a.packed_f32 = reinterpret_cast<const float*>(packed);
-    a.packed_b16 = reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(packed) + uv_taylor_temp_bytes());
-    hipLaunchKernelGGL(k_uv_taylor_mixed, dim3((N + UV_P - 1) / UV_P), dim3(256), 0, s, a, xyz, N, uvs, grad_uvs);
     return (int)hipGetLastError();
 }

@@ -6,7 +6,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TEXGS_LIB") or os.path.join(os.path.dirname(_HERE), "libtexgs.so")   # TEXGS_LIB: experiment builds only
 
-ABI_VERSION = 18
+ABI_VERSION = 19
 TILE = 16
 REC_TEST_FLOATS = 8
 REC_SHADE_FLOATS = 20
@@ -73,12 +73,15 @@ class UVNetGradStruct(C.Structure):
     _fields_ = [(n, _fp) for n in ("dW1", "db1", "dW2", "db2", "dW3", "db3", "dW4", "db4", "dW5", "db5")]
 
 
+UV_PRECISION = {"fp32": 0, "bf16x3": 1, "mixed": 2}          # TEXGS_UV_FP32 / _BF16X3 / _MIXED
+
+
 EXPORTS = ["texgs_abi_version", "texgs_build_id", "texgs_last_error", "texgs_scan_temp_bytes", "texgs_sort_temp_bytes",
            "texgs_preprocess_forward", "texgs_num_rendered_words", "texgs_num_rendered_begin", "texgs_num_rendered_reduce", "texgs_depth_sort_scan", "texgs_bin_sort_render_forward",
            "texgs_render_forward", "texgs_backward", "texgs_backward_render", "texgs_backward_preprocess",
            "texgs_rgb_alpha_loss", "texgs_mark_visible", "texgs_profile_enable", "texgs_tex_bin_count",
-           "texgs_profile_read", "texgs_profile_select", "texgs_selftest_waveops", "texgs_geom_losses", "texgs_norm_from_depth", "texgs_uv_taylor", "texgs_uv_taylor_temp_bytes", "texgs_uv_pack", "texgs_uv_taylor_packed",
-           "texgs_uv_pack_bf16x3", "texgs_uv_taylor_packed_bf16x3", "texgs_uv_backward", "texgs_uv_backward_mixed", "texgs_uv_backward_temp_bytes", "texgs_uv_pack_mixed", "texgs_uv_taylor_packed_mixed",
+           "texgs_profile_read", "texgs_profile_select", "texgs_selftest_waveops", "texgs_geom_losses", "texgs_norm_from_depth",
+           "texgs_uv_packed_bytes", "texgs_uv_pack", "texgs_uv_taylor_packed", "texgs_uv_backward", "texgs_uv_backward_temp_bytes",
            "texgs_hashgrid_levels", "texgs_hashgrid_forward", "texgs_hashgrid_backward_temp_bytes", "texgs_hashgrid_backward",
            "texgs_chamfer_nn_temp_bytes", "texgs_chamfer_nn",
            "texgs_knn3_temp_bytes", "texgs_knn3_mean_dist2", "texgs_fps_temp_bytes", "texgs_farthest_points",
@@ -133,30 +136,19 @@ def load():
     lib.texgs_geom_losses.argtypes = [C.c_void_p] * 6 + [C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.texgs_geom_losses.restype = C.c_int
-    lib.texgs_uv_taylor_temp_bytes.restype = C.c_size_t
     lib.texgs_norm_from_depth.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_int32, C.c_int32, C.c_float,
                                           C.c_void_p, C.c_void_p, C.c_void_p]
     lib.texgs_norm_from_depth.restype = C.c_int
-    lib.texgs_uv_taylor.argtypes = [P(UVNetStruct), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.texgs_uv_taylor.restype = C.c_int
-    lib.texgs_uv_pack.argtypes = [P(UVNetStruct), C.c_void_p, C.c_void_p]
+    lib.texgs_uv_packed_bytes.argtypes = [C.c_int32]
+    lib.texgs_uv_packed_bytes.restype = C.c_size_t
+    lib.texgs_uv_pack.argtypes = [P(UVNetStruct), C.c_int32, C.c_void_p, C.c_void_p]
     lib.texgs_uv_pack.restype = C.c_int
-    lib.texgs_uv_taylor_packed.argtypes = [P(UVNetStruct), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.texgs_uv_taylor_packed.argtypes = [P(UVNetStruct), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.texgs_uv_taylor_packed.restype = C.c_int
-    lib.texgs_uv_pack_bf16x3.argtypes = [P(UVNetStruct), C.c_void_p, C.c_void_p]
-    lib.texgs_uv_pack_bf16x3.restype = C.c_int
-    lib.texgs_uv_taylor_packed_bf16x3.argtypes = [P(UVNetStruct), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.texgs_uv_taylor_packed_bf16x3.restype = C.c_int
-    lib.texgs_uv_pack_mixed.argtypes = [P(UVNetStruct), C.c_void_p, C.c_void_p]
-    lib.texgs_uv_pack_mixed.restype = C.c_int
-    lib.texgs_uv_taylor_packed_mixed.argtypes = [P(UVNetStruct), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.texgs_uv_taylor_packed_mixed.restype = C.c_int
     lib.texgs_uv_backward_temp_bytes.argtypes = [C.c_int32]
     lib.texgs_uv_backward_temp_bytes.restype = C.c_size_t
-    lib.texgs_uv_backward.argtypes = [P(UVNetStruct), C.c_void_p, C.c_void_p, C.c_int32, P(UVNetGradStruct), C.c_void_p, C.c_void_p]
+    lib.texgs_uv_backward.argtypes = [P(UVNetStruct), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, P(UVNetGradStruct), C.c_void_p, C.c_void_p]
     lib.texgs_uv_backward.restype = C.c_int
-    lib.texgs_uv_backward_mixed.argtypes = lib.texgs_uv_backward.argtypes
-    lib.texgs_uv_backward_mixed.restype = C.c_int
     lib.texgs_hashgrid_levels.argtypes = [P(HashGridStruct), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, P(C.c_uint32)]
     lib.texgs_hashgrid_levels.restype = C.c_int
     lib.texgs_hashgrid_forward.argtypes = [P(HashGridStruct), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]

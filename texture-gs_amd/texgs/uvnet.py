@@ -8,7 +8,7 @@ FullyFusedMLP networks, whose state_dict is ONE flat `params` tensor per network
 
 Three ways to evaluate:
   forward(xyz, emb)                       plain torch, differentiable (any device)
-  uv_and_jacobian(xyz, emb)               the fused HIP kernel (csrc/uvnet.hip, fp32 MFMA): phi and its analytic 3x3 Jacobian by
+  uv_and_jacobian(xyz, emb)               the fused HIP kernel (csrc/uvnet.hip): phi and its analytic 3x3 Jacobian by
                                           forward-mode propagation in one launch, instead of UVNet.forward plus the three backward
                                           passes of torch.autograd.functional.jacobian (models/texture_gaussian3d.py:216-236)
   uvs_and_jacobian_with_grad(xyz, emb)    the same launch inside an autograd node: `uvs` carries gradients to xyz (= J^T g, free:
@@ -189,21 +189,19 @@ class UVNet(nn.Module):
         p = lambda t: None if t is None else t.data_ptr()
         net = _lib.UVNetStruct(*[p(t) for t in ws], HIDDEN)
         stream = torch.cuda.current_stream(dev).cuda_stream
-        split = self.precision
-        pack_fn, eval_fn = {"fp32": (lib.texgs_uv_pack, lib.texgs_uv_taylor_packed),
-                            "bf16x3": (lib.texgs_uv_pack_bf16x3, lib.texgs_uv_taylor_packed_bf16x3),
-                            "mixed": (lib.texgs_uv_pack_mixed, lib.texgs_uv_taylor_packed_mixed)}[split]
-        key = tuple((t.data_ptr(), t._version) for t in (self.pre_mlp[2].weight, self.mlp[0].weight, self.mlp[2].weight)) + (dev, split)
+        prec = _lib.UV_PRECISION[self.precision]
+        key = tuple((t.data_ptr(), t._version) for t in (self.pre_mlp[2].weight, self.mlp[0].weight, self.mlp[2].weight)) + (dev, prec)
         uvs = torch.empty(N, 3, dtype=torch.float32, device=dev)
         juv = torch.empty(N, 9, dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
             slot = (dev.index, int(stream))
             ent = self._packed.get(slot)
             if ent is None or ent[0] != key:
-                buf = ent[1] if ent is not None else torch.empty(2 * lib.texgs_uv_taylor_temp_bytes(), dtype=torch.uint8, device=dev)   # ("mixed" holds both layouts)
-                _lib.check(pack_fn(C.byref(net), p(buf), stream), "texgs_uv_pack")       # (re-packed in place: same stream, in order)
+                nbytes = lib.texgs_uv_packed_bytes(prec)           # ("mixed" holds both layouts)
+                buf = ent[1] if ent is not None and ent[1].numel() == nbytes else torch.empty(nbytes, dtype=torch.uint8, device=dev)
+                _lib.check(lib.texgs_uv_pack(C.byref(net), prec, p(buf), stream), "texgs_uv_pack")       # (re-packed in place: same stream, in order)
                 self._packed[slot] = ent = (key, buf)
-            _lib.check(eval_fn(C.byref(net), p(ent[1]), p(x), N, p(uvs), p(juv), stream), "texgs_uv_taylor_packed")
+            _lib.check(lib.texgs_uv_taylor_packed(C.byref(net), prec, p(ent[1]), p(x), N, p(uvs), p(juv), stream), "texgs_uv_taylor_packed")
         return uvs, juv
 
     @torch.no_grad()
@@ -233,8 +231,8 @@ class UVNet(nn.Module):
             gr = _lib.UVNetGradStruct(*[p(t) for t in outs])
             # precision "fp32": all nine GEMMs on the f32-input MFMA; "mixed" / "bf16x3": the forward recomputation in f32 (the
             # forward launch's ReLU masks bit for bit), the six GEMMs of the backward chain as split-bf16 products (~1e-5 relative)
-            fn = lib.texgs_uv_backward if self.precision == "fp32" else lib.texgs_uv_backward_mixed
-            _lib.check(fn(C.byref(netp), p(x), p(gg), N, C.byref(gr), p(temp), stream), "texgs_uv_backward")
+            prec = _lib.UV_PRECISION[self.precision]
+            _lib.check(lib.texgs_uv_backward(C.byref(netp), prec, p(x), p(gg), N, C.byref(gr), p(temp), stream), "texgs_uv_backward")
         return outs
 
     def uvs_and_jacobian_with_grad(self, xyz, emb):
