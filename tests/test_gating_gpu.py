@@ -370,3 +370,99 @@ def test_train_eval_interleave_costs_one_late_handoff_per_switch_and_holds_no_mo
     finally:
         RZ.reset_handoff_predictor()
         RZ.release_scratch()
+
+
+def _launches(fn):
+    """(kernel launches of fn() by kernel name, as the library's HIP-event profiler counted them; fn's result)"""
+    from texgs import _lib
+    _lib.profile_read()
+    res = fn()
+    return {k: n for k, (_, n) in _lib.profile_read().items() if n}, res
+
+
+def test_host_paths_launch_the_same_kernels(lib_built):
+    """Which kernels each path of the host layer launches, and how often (texgs/rasterizer.py: eager and lazy hand-off, the three
+    backward flavours, shared and rebuilt geometry, a prefetched forward, the untextured surface), and what becomes of a prefetched
+    forward that is displaced unfinished: the host has waited for its readback and its pinned buffer is back in the pool."""
+    import gc
+    from texgs import _lib
+    from texgs import rasterizer as RZ
+    from texgs.rasterizer import GaussianRasterizer, forward_raw, backward_raw, prefetch_forward
+    H, W, N = 40, 72, 600
+    dev, scene, st, target, nhat = _setup(N=N, R=32, W=W, H=H)
+    t = lambda x: x.to(dev)
+    args = [t(scene.means3D), t(scene.shs), t(scene.opacities), t(scene.scales), t(scene.rotations), t(scene.uvs),
+            t(scene.gradient_uvs), t(scene.texture)]
+    dimg = (torch.randn(3, H, W, generator=torch.Generator().manual_seed(1)) * 1e-4).to(dev)
+    k1, k6 = dict(preprocess_fwd=1), dict(render_fwd=1)
+    lists = dict(duplicate=1, sort=1, ranges=1)
+    six = dict(k1, scan=1, **lists, **k6)
+    k7, red, k8 = dict(render_bwd=1), dict(texgrad_reduce=1), dict(preprocess_bwd=1)
+    stats = RZ.geometry_cache_stats
+    gc.collect()
+    RZ.release_scratch()
+    RZ.reset_handoff_predictor()
+    saved = RZ.GEOM_CACHE
+    _lib.profile_enable(True)
+    try:
+        # an eager forward and the three flavours of its backward
+        got, (_, s) = _launches(lambda: forward_raw(st, *args, lazy=False))
+        assert s.D > 0 and got == six, got
+        for want, expect in ((_lib.WANT_ALL, dict(k7, **red, **k8)), (_lib.WANT_TEXTURE, dict(k7, **red)), (_lib.WANT_GAUSSIANS, dict(k7, **k8))):
+            got, _ = _launches(lambda: backward_raw(s, dimg, None, None, None, want=want))
+            assert got == expect, (want, got)
+        # the same view again shares the lists; the same sizes with one input changed in place does not
+        s0 = stats()
+        got, (_, s2) = _launches(lambda: forward_raw(st, *args, lazy=False))
+        assert got == dict(k1, **k6) and s2.shared_geometry and stats()["hits"] == s0["hits"] + 1, got
+        args[0].add_(1e-3)
+        got, (_, s3) = _launches(lambda: forward_raw(st, *args, lazy=False))
+        assert got == six and not s3.shared_geometry and stats()["misses"] == s0["misses"] + 1, got
+        # a forward begun early, then finished by the matching call
+        RZ.release_scratch()
+        got, _ = _launches(lambda: prefetch_forward(st, *args))
+        assert got == dict(k1, scan=1) and sum(len(v) for v in RZ._PREFETCH.values()) == 1, got
+        got, _ = _launches(lambda: forward_raw(st, *args))
+        assert got == dict(lists, **k6) and not RZ._PREFETCH, (got, RZ._PREFETCH)
+        # the untextured surface
+        RZ.release_scratch()
+        got, (_, su) = _launches(lambda: forward_raw(st, *args[:5], None, None, None))
+        assert got == six, got
+        got, _ = _launches(lambda: backward_raw(su, dimg, None, None, None))
+        assert got == dict(k7, **k8), got
+        # autograd forwards whose graphs are dropped leave the hand-off to the backward: it costs that backward one more K6
+        RZ.GEOM_CACHE = False                  # (every call here is the same view: keep the two mechanisms apart)
+        RZ.release_scratch()
+        leaves = {n: getattr(scene, n).clone().to(dev).requires_grad_(True) for n in NAMES}
+        fwd = lambda: GaussianRasterizer(st)(means3D=leaves["means3D"], means2D=None, shs=leaves["shs"], opacities=leaves["opacities"],
+                                             scales=leaves["scales"], rotations=leaves["rotations"], uvs=leaves["uvs"],
+                                             gradient_uvs=args[6], texture=leaves["texture"], extra_attrs=None)
+        for _ in range(2):
+            out = fwd()
+            del out
+        assert RZ.unused_streak(dev.index) >= 2
+        h0 = stats()["late_handoffs"]
+        got, out = _launches(fwd)
+        assert got == six, got
+        got, _ = _launches(lambda: synth.synthetic_loss(out[0], out[3], out[2], target, nhat).backward())
+        assert got == dict(k6, **k7, **red, **k8) and stats()["late_handoffs"] == h0 + 1, got
+        RZ.GEOM_CACHE = saved
+        # five forwards begun on one stream: four stay pending; the first was abandoned -- its readback has completed and its pinned
+        # buffer went back to the pool only then
+        RZ.release_scratch()
+        pool = RZ._PIN_POOL.setdefault(int(_lib.load().texgs_num_rendered_words(N)), [])
+        del pool[:]
+        for k in range(5):
+            prefetch_forward(st._replace(scale_modifier=1.0 + 0.01 * k), *args)
+            if k == 0:
+                (pending,) = RZ._PREFETCH.values()
+                first = pending[0][1]
+        assert len(pending) == 4 and all(f is not first for _, f in pending)
+        assert first.d_ev.query()
+        assert len(pool) == 1 and pool[0] is first.pin
+    finally:
+        _lib.profile_enable(False)
+        RZ.GEOM_CACHE = saved
+        RZ.reset_handoff_predictor()
+        RZ.release_scratch()
+    assert not RZ._PREFETCH

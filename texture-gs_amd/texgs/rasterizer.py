@@ -7,6 +7,10 @@ bookkeeping); all arithmetic runs in the hand-written gfx950 kernels.
 """
 import ctypes as C
 import math
+import os as _os
+import threading as _threading
+from collections import namedtuple
+from types import SimpleNamespace
 from typing import NamedTuple, Optional
 
 import torch
@@ -14,8 +18,6 @@ from torch import nn
 
 from . import _lib
 
-
-import os as _os
 USE_TEX_BINS = _os.environ.get("TEXGS_TEX_BINS", "1") != "0"       # binned two-pass texture gradient
 TEX_REC_CAP = int(_os.environ.get("TEXGS_REC_CAP", "0"))           # fixed record capacity (tests); 0 = adaptive
 # OPT-IN fast path: add into a leaf's existing .grad in place instead of handing autograd a temporary.  Off by default because
@@ -59,23 +61,66 @@ def _f32c(t: torch.Tensor, name: str, device) -> torch.Tensor:
     return t.contiguous()
 
 
+class _Arena:
+    """One device allocation carved into named, 256-byte-aligned pieces."""
+
+    def __init__(self, device):
+        self.device, self.specs, self.size, self.buf = device, {}, 0, None
+
+    def add(self, name, shape, dtype):
+        off = (self.size + 255) & ~255
+        self.specs[name] = (off, tuple(shape), dtype)
+        self.size = off + math.prod(shape) * dtype.itemsize
+
+    def commit(self):
+        self.buf = torch.empty(max(self.size, 1), dtype=torch.uint8, device=self.device)
+
+    def ptr(self, name):
+        return self.buf.data_ptr() + self.specs[name][0] if name in self.specs else None
+
+    def view(self, name):
+        off, shape, dtype = self.specs[name]
+        return self.buf[off:off + math.prod(shape) * dtype.itemsize].view(dtype).view(shape)
+
+
+class _Tensors(dict):
+    """What a forward leaves behind, by name: real tensors (inputs kept alive, outputs) plus views into the arenas, made on
+    first access.  A name that was not allocated (e.g. the survivor lists of a forward-only call) reads as None."""
+
+    def __init__(self, arenas, **real):
+        super().__init__(**real)
+        self._arenas = arenas
+
+    def __missing__(self, name):
+        for ar in self._arenas:
+            if name in ar.specs:
+                self[name] = v = ar.view(name)
+                return v
+        self[name] = None
+        return None
+
+    def get(self, name, default=None):
+        v = self[name]
+        return default if v is None else v
+
+
 # Two forwards of the same geometry share the tile binning and K6's survivor lists (the reference renders every training view
 # twice: models/texture_gaussian3d.py:318 and :375-389 -- same camera, same Gaussians, sh_degree 0 the second time; visual_step
 # :499-511 likewise).  Decided by K1's geometry fingerprint (texgs.h texgs_num_rendered_reduce), so recomputed activations
 # (sigmoid / exp outputs are new tensors on every render() call) share too.  One entry per (device, stream).
 GEOM_CACHE = _os.environ.get("TEXGS_GEOM_CACHE", "1") != "0"
+_CAPACITY_HINT = {}
+_GEOM = {}                  # (device index, stream) -> _GeomEntry of the last forward that built lists there
+_GeomEntry = namedtuple("_GeomEntry", "ints cam_key fingerprint D cap bin arenas handoff counts")
+_GEOM_STATS = {"hits": 0, "misses": 0, "late_handoffs": 0}
 # A forward that autograd may or may not differentiate (retexture.py:27 / visual_step build a graph and never call backward)
 # leaves K6's hand-off to the backward once two graphs in a row were dropped unused; the first backward that does arrive
 # produces the hand-off itself (one more K6) and switches the forwards back.
-LAZY_HANDOFF = _os.environ.get("TEXGS_LAZY_HANDOFF", "1") != "0"
-_CAPACITY_HINT = {}
-_GEOM = {}                  # (device index, stream) -> _GeomEntry of the last forward that built lists there
-# the hand-off predictor: autograd forwards are numbered; per device, the highest number whose backward ran and the numbers of
+# The predictor: autograd forwards are numbered; per device, the highest number whose backward ran and the numbers of
 # those dropped without one.  (Order-independent: a state that the garbage collector frees late cannot reset the streak.)
 _SERIAL = [0]
 _LAST_DIFFERENTIATED = {}
 _DROPPED = {}
-import threading as _threading
 _PRED_LOCK = _threading.RLock()       # the predictor's dicts are touched from __del__ (any thread, any time the collector runs)
 
 
@@ -92,16 +137,11 @@ def reset_handoff_predictor():
         _DROPPED.clear()
 
 
-class _GeomEntry:
-    __slots__ = ("ints", "cam_key", "fingerprint", "D", "bin", "arenas", "handoff", "counts", "cap")
-
-
 def geometry_cache_stats():
     """{'hits': n, 'misses': n} of the shared-geometry path since import (diagnostics / tests)."""
     return dict(_GEOM_STATS)
 
 
-_GEOM_STATS = {"hits": 0, "misses": 0, "late_handoffs": 0}
 # Backward scratch, ONE entry per (device, HIP stream): the moment accumulators (grow-only, sliced [:N]; all-zero between
 # calls: K8 clears what it read) and the texture-gradient bins of the last resolution used on that stream.  A stream runs
 # its views in order, so its scratch is never shared by two views in flight.  release_scratch() drops entries (ViewPipeline
@@ -109,19 +149,13 @@ _GEOM_STATS = {"hits": 0, "misses": 0, "late_handoffs": 0}
 _SCRATCH = {}
 
 
-class _StreamScratch:
-    __slots__ = ("acc", "bins")
-
-    def __init__(self):
-        self.acc = None
-        self.bins = None
-
-
 def release_scratch(device=None, stream=None):
     """Free the backward scratch and the shared-geometry entry cached for (device, stream); None = every device / stream."""
     for cache in (_SCRATCH, _GEOM, _PREFETCH):
         for key in list(cache):
             if (device is None or key[0] == torch.device(device).index) and (stream is None or key[1] == int(stream)):
+                for _, fwd in (cache[key] if cache is _PREFETCH else ()):
+                    fwd.abandon()
                 del cache[key]
 
 
@@ -200,13 +234,22 @@ class _TexBins:
 class _State:
     """Everything one forward leaves behind for its backward (per call: no global scratch, two forwards may
     be alive before a backward, models/texture_gaussian3d.py:318,378,410)."""
-    __slots__ = ("frame", "inputs", "geom", "bin", "img", "tensors", "N", "K", "R", "H", "W", "D", "cap", "tiles",
+    __slots__ = ("frame", "inputs", "geom", "bin", "img", "tensors", "args", "N", "K", "R", "H", "W", "D", "cap", "tiles",
                  "want_counts", "lazy", "backward_ran", "shared_geometry", "serial", "__weakref__")
 
-    def __del__(self):          # the forwards' hand-off predictor (LAZY_HANDOFF): was this autograd forward ever differentiated?
+    def __init__(self, frame, inputs, geom, bin, img, tensors, args, D, cap, tiles, want_counts, lazy, shared_geometry):
+        self.frame, self.inputs, self.geom, self.bin, self.img, self.tensors, self.args = frame, inputs, geom, bin, img, tensors, args
+        self.N, self.K, self.R, self.H, self.W = args.N, args.K, args.R, frame.image_height, frame.image_width
+        self.D, self.cap, self.tiles = D, cap, tiles
+        self.want_counts, self.lazy, self.backward_ran, self.shared_geometry = want_counts, lazy, False, shared_geometry
+        with _PRED_LOCK:
+            _SERIAL[0] += 1
+            self.serial = _SERIAL[0]
+
+    def __del__(self):          # the forwards' hand-off predictor: was this autograd forward ever differentiated?
         try:
             if getattr(self, "lazy", False) and not self.backward_ran:
-                dev = self.tensors["keep"][0].device.index
+                dev = self.args.means3D.device.index
                 with _PRED_LOCK:
                     last = _LAST_DIFFERENTIATED.get(dev, -1)
                     _DROPPED[dev] = [n for n in _DROPPED.get(dev, []) if n > last][-8:] + [self.serial]
@@ -215,7 +258,6 @@ class _State:
 
 
 def _make_frame(st: GaussianRasterizationSettings, N, K, R, device, keep):
-    H, W = int(st.image_height), int(st.image_width)
     bg = _f32c(st.bg, "bg", device).reshape(-1)
     vm = _f32c(st.viewmatrix, "viewmatrix", device).reshape(-1)
     pm = _f32c(st.projmatrix, "projmatrix", device).reshape(-1)
@@ -223,9 +265,8 @@ def _make_frame(st: GaussianRasterizationSettings, N, K, R, device, keep):
     if bg.numel() != 3 or vm.numel() != 16 or pm.numel() != 16 or cp.numel() != 3:
         raise ValueError("bg/campos must have 3 elements and viewmatrix/projmatrix 16")
     keep.extend([bg, vm, pm, cp])
-    f = _lib.Frame(H, W, float(st.tanfovx), float(st.tanfovy), float(st.scale_modifier), int(st.sh_degree),
-                   int(K), int(R), int(N), 1 if st.debug else 0, _ptr(bg), _ptr(vm), _ptr(pm), _ptr(cp))
-    return f
+    return _lib.Frame(int(st.image_height), int(st.image_width), float(st.tanfovx), float(st.tanfovy), float(st.scale_modifier),
+                      int(st.sh_degree), int(K), int(R), int(N), 1 if st.debug else 0, _ptr(bg), _ptr(vm), _ptr(pm), _ptr(cp))
 
 
 # ---- forward prefetch: K1 (+ the D readback, + K2) of a LATER view issued early ---------------------------------------------------
@@ -236,7 +277,7 @@ def _make_frame(st: GaussianRasterizationSettings, N, K, R, device, keep):
 # of a view AHEAD of the backward that is about to be queued on the same stream; when that view's forward is called, with the same
 # tensors (same storage, same version counters) and settings, its D arrived long ago and nothing waits.  One pending forward per key;
 # a forward that does not match anything pending runs as usual.
-_PREFETCH = {}             # (device index, stream) -> [(key, finish closure)]
+_PREFETCH = {}             # (device index, stream) -> [(key, _Forward that has begun)]; a stream without pending forwards has no entry
 _PIN_POOL = {}             # words -> [pinned int32 tensors]
 
 
@@ -251,59 +292,26 @@ def _pin_give(t):
         pool.append(t)
 
 
-def _prefetch_key(st, tensors, flags):
-    t = lambda x: None if x is None else (x.data_ptr(), x._version, tuple(x.shape), x.requires_grad)
-    return (int(st.image_height), int(st.image_width), float(st.tanfovx), float(st.tanfovy), float(st.scale_modifier), int(st.sh_degree),
-            bool(st.debug), t(st.bg), t(st.viewmatrix), t(st.projmatrix), t(st.campos)) + tuple(t(x) for x in tensors) + tuple(flags)
-
-
 def _prefetch_take(device, key):
-    lst = _PREFETCH.get((device.index, int(torch.cuda.current_stream(device).cuda_stream)))
-    if not lst:
-        return None
-    for k, (key_k, fin) in enumerate(lst):
+    skey = (device.index, int(torch.cuda.current_stream(device).cuda_stream))
+    lst = _PREFETCH.get(skey, ())
+    for k, (key_k, fwd) in enumerate(lst):
         if key_k == key:
             del lst[k]
-            return fin
-    return None
+            if not lst:
+                del _PREFETCH[skey]
+            return fwd
 
 
-def prefetch_forward(st, means3D, shs, opacities, scales, rotations, uvs, gradient_uvs, texture, color_offset=None,
-                     for_backward=True, cov3D_precomp=None, count_bins=None, lazy=False):
-    """Begin a forward now -- K1, the asynchronous D readback, K2 -- on the current stream; a later forward_raw / GaussianRasterizer
-    call on this stream with the same arguments (same tensor storages and versions, same settings, same flags) finishes it without
-    waiting for the device.  At most four forwards are kept pending per stream (older ones are dropped: their K1 was wasted, nothing
-    else).  Returns nothing."""
-    fin = forward_raw(st, means3D, shs, opacities, scales, rotations, uvs, gradient_uvs, texture, color_offset, for_backward,
-                      cov3D_precomp, count_bins, lazy, _begin_only=True)
-    key = _prefetch_key(st, (means3D, shs, opacities, scales, rotations, uvs, gradient_uvs, texture, color_offset, cov3D_precomp),
-                        (for_backward, count_bins, lazy))
-    lst = _PREFETCH.setdefault((means3D.device.index, int(torch.cuda.current_stream(means3D.device).cuda_stream)), [])
-    lst.append((key, fin))
-    del lst[:-4]
+# a forward's inputs after _check_inputs: contiguous float32 tensors (None where absent) and the sizes they imply
+_Args = namedtuple("_Args", "means3D shs opacities scales rotations uvs gradient_uvs texture color_offset cov3D_precomp N K R")
+# TexGSImage's K6 -> K7 hand-off pointers; the arena pieces (_add_handoff) carry the same names
+_HANDOFF = tuple(n for n, _ in _lib.Image._fields_[6:])
 
 
-def forward_raw(st, means3D, shs, opacities, scales, rotations, uvs, gradient_uvs, texture, color_offset=None,
-                for_backward=True, cov3D_precomp=None, count_bins=None, lazy=False, _begin_only=False):
-    """Run K1..K6.  Returns (outputs, state).  No autograd here.
-
-    `lazy` (the autograd path sets it): the hand-off may be left to the backward (see LAZY_HANDOFF).
-
-    `for_backward`: K6 leaves the per-block survivor lists its backward replays.  `count_bins` (default: for_backward and
-    there is a texture): K6 also counts the texture-gradient footprints per texture bin (the exact list sizes of
-    backward_raw's binned texture gradient); a caller that will not ask for dL/dtexture saves that work.
-    `texture=None`: the untextured surface (diff_gauss, render/render.py:75-84): uvs / gradient_uvs may be None too.
-    `cov3D_precomp` f32[N,6] (untextured surface only): used instead of scales / rotations."""
-    lib = _lib.load()
+def _check_inputs(st, means3D, shs, opacities, scales, rotations, uvs, gradient_uvs, texture, color_offset=None, cov3D_precomp=None):
+    """Types, dtypes, shapes and devices of a forward's inputs -> _Args.  Pure: no library call, tensors of any one device."""
     device = means3D.device
-    if device.type != "cuda":
-        raise RuntimeError("the textured rasterizer runs on an AMD GPU (torch device 'cuda' = HIP); "
-                           f"got tensors on {device}. There is no CPU fallback.")
-    if _PREFETCH and not _begin_only:        # was this very forward begun earlier (prefetch_forward)?  Then K1 ran long ago: finish it
-        pend = _prefetch_take(device, _prefetch_key(st, (means3D, shs, opacities, scales, rotations, uvs, gradient_uvs, texture,
-                                                         color_offset, cov3D_precomp), (for_backward, count_bins, lazy)))
-        if pend is not None:
-            return pend()
     N = means3D.shape[0]
     means3D = _f32c(means3D, "means3D", device)
     if means3D.dim() != 2 or means3D.shape[1] != 3:
@@ -337,9 +345,6 @@ def forward_raw(st, means3D, shs, opacities, scales, rotations, uvs, gradient_uv
     else:
         uvs = gradient_uvs = None
         R = 1
-    if count_bins is None:
-        count_bins = for_backward
-    count_bins = bool(count_bins and for_backward and texture is not None)
     K = 0
     if shs is not None:
         shs = _f32c(shs, "shs", device)
@@ -354,252 +359,282 @@ def forward_raw(st, means3D, shs, opacities, scales, rotations, uvs, gradient_uv
             raise ValueError(f"color_offset must be [N,3], got {tuple(color_offset.shape)}")
     if int(st.sh_degree) < 0 or int(st.sh_degree) > 3:
         raise ValueError("sh_degree must be in [0,3]")
-    H, W = int(st.image_height), int(st.image_width)
-    tiles = ((W + _lib.TILE - 1) // _lib.TILE) * ((H + _lib.TILE - 1) // _lib.TILE)
-    cur_stream = torch.cuda.current_stream(device)
-    stream = cur_stream.cuda_stream
-    keep = [means3D, shs, opacities, scales, rotations, uvs, gradient_uvs, texture, color_offset, cov3D_precomp]
-    handoff = bool(for_backward) and not (lazy and LAZY_HANDOFF and unused_streak(device.index) >= 2)
-    want_counts = bool(count_bins and USE_TEX_BINS)
+    return _Args(means3D, shs, opacities, scales, rotations, uvs, gradient_uvs, texture, color_offset, cov3D_precomp, N, K, R)
 
-    with torch.cuda.device(device):
-        frame = _make_frame(st, N, K, R, device, keep)
-        inputs = _lib.Inputs(_ptr(means3D), _ptr(shs), _ptr(opacities), _ptr(scales), _ptr(rotations),
-                             _ptr(uvs), _ptr(gradient_uvs), _ptr(texture), _ptr(color_offset), _ptr(cov3D_precomp))
-        i32, f32, u8 = torch.int32, torch.float32, torch.uint8
-        n1 = max(N, 1)
-        # a forward that may share an earlier one's lists: same sizes, same camera tensors -- K1's fingerprint decides
-        gints = (N, H, W, R if texture is not None else 0, float(st.tanfovx), float(st.tanfovy), float(st.scale_modifier),
-                 cov3D_precomp is not None)
-        cam_key = tuple((t.data_ptr(), t._version) for t in (st.viewmatrix, st.projmatrix, st.campos))
-        gkey = (device.index, int(stream))
-        entry = _GEOM.get(gkey) if GEOM_CACHE else None
-        candidate = entry is not None and entry.ints == gints and entry.cam_key == cam_key
-        if entry is not None and not candidate:     # another view / size: the old lists cannot be shared any more -- let go of their
-            del _GEOM[gkey]                         # arenas before this forward allocates its own (they stay alive only while a
-            entry = None                            # state that shares them does)
-        # Everything the kernels keep between forward and backward lives in TWO allocations (one sized by N / the image, one by
-        # the instance capacity): ~20 separate torch.empty calls were ~0.1 ms of host time per view.  Tensor views of the
-        # pieces are made on demand (tests, diagnostics).
-        scan_bytes = lib.texgs_scan_temp_bytes(N)
-        fix = _Arena(device)
-        fix.add("rec", (n1, _lib.REC_TEST_FLOATS), f32)          # test records: xy, conic, opacity, cull aids
-        fix.add("rec_shade", (n1, _lib.REC_SHADE_FLOATS), f32)
-        fix.add("depth", (n1,), f32)
-        fix.add("rect", (n1, 2), i32)
-        fix.add("tiles_touched", (n1,), i32)
-        fix.add("offsets", (n1,), i32)
-        fix.add("scan_temp", (scan_bytes,), u8)
-        fix.add("final_T", (H, W), f32)
-        fix.add("n_contrib", (H, W), i32)
 
-        def add_lists(ar):              # per-tile pieces of the lists (the candidate path adds them only if it has to build lists)
-            ar.add("ranges", (tiles, 2), i32)              # zero-filled by K3
-            ar.add("tile_order", (tiles,), i32)
-            if want_counts and handoff:
-                ar.add("tex_bin_count", (2 * int(lib.texgs_tex_bin_count(R)),), i32)     # reserved | overflow footprints per bin
-                ar.add("tex_bin_resv", (4 * tiles, _lib.RESV_WORDS), i32)      # K6's per-block reservations in the record lists
-            if handoff:
-                ar.add("surv_count", (4 * tiles,), i32)
-        if not candidate:
-            add_lists(fix)
-        fix.commit()
-        radii = torch.empty(N, dtype=i32, device=device)          # K1 writes every entry (0 for culled)
-        geom = _lib.Geom(fix.ptr("rec"), fix.ptr("rec_shade"), fix.ptr("depth"), _ptr(radii), fix.ptr("rect"),
-                         fix.ptr("tiles_touched"), fix.ptr("offsets"), fix.ptr("scan_temp"), scan_bytes)
-        # everything is allocated BEFORE the one device->host sync, the D-sized buffers from a capacity hint
-        # (largest D seen on this device x 1.25): K1 -> sync (K2 runs meanwhile) -> K3..K6 with little host work between
-        out_color = torch.empty(3, H, W, dtype=f32, device=device)
-        out_depth = torch.empty(1, H, W, dtype=f32, device=device)
-        out_norm = torch.empty(3, H, W, dtype=f32, device=device)
-        out_alpha = torch.empty(1, H, W, dtype=f32, device=device)
-        img = _lib.Image(_ptr(out_color), _ptr(out_depth), _ptr(out_norm), _ptr(out_alpha), fix.ptr("final_T"),
-                         fix.ptr("n_contrib"), None, None, None, None, None)
+def _add_handoff(ar, cap, tiles, R, want_counts):
+    """The K6 -> K7 hand-off of the per-block survivor lists, laid out in this ONE place: the pieces sized by the instance capacity
+    (`cap`; None = not in this arena) and the per-tile ones (`tiles`; None = not in this arena)."""
+    if cap is not None:         # four blocks per tile, each at most the tile's list length
+        ar.add("survivors", (4 * max(cap, 1), 2), torch.int32)
+        ar.add("surv_qmask", (4 * max(cap, 1),), torch.int16)
+    if tiles is not None:
+        ar.add("surv_count", (4 * tiles,), torch.int32)
+        if want_counts:
+            ar.add("tex_bin_count", (2 * int(_lib.load().texgs_tex_bin_count(R)),), torch.int32)     # reserved | overflow footprints per bin
+            ar.add("tex_bin_resv", (4 * tiles, _lib.RESV_WORDS), torch.int32)      # K6's per-block reservations in the record lists
 
-        def alloc_bin(cap, lists_ar):
-            c1 = max(cap, 1)
-            sort_bytes = lib.texgs_sort_temp_bytes(cap, tiles)
-            ar = _Arena(device)
-            ar.add("keys_unsorted", (c1,), torch.int64)
-            ar.add("keys_sorted", (c1,), torch.int64)
-            ar.add("point_list", (c1,), i32)
-            ar.add("sort_temp", (sort_bytes,), u8)
-            if lists_ar is None:
-                add_lists(ar)
-            if handoff:        # K6 -> K7 hand-off of the per-block survivor lists: four blocks per tile, each at most the tile's list length
-                ar.add("survivors", (4 * c1, 2), i32)
-                ar.add("surv_qmask", (4 * c1,), torch.int16)
-            ar.commit()
-            la = lists_ar if lists_ar is not None else ar
-            b = _lib.Binning(0, ar.ptr("keys_unsorted"), ar.ptr("keys_sorted"), ar.ptr("point_list"), la.ptr("ranges"),
-                             la.ptr("tile_order"), ar.ptr("sort_temp"), sort_bytes)
-            img.tex_bin_count, img.surv_count = la.ptr("tex_bin_count"), la.ptr("surv_count")
-            img.tex_bin_resv = la.ptr("tex_bin_resv")
-            img.survivors, img.surv_qmask = ar.ptr("survivors"), ar.ptr("surv_qmask")
-            return b, ar
-        hint_key = (device.index, N, H, W)
-        cap = _CAPACITY_HINT.get(hint_key, max(4 * N, 1024))
-        binning = bin_ar = None
-        if not candidate:
-            binning, bin_ar = alloc_bin(cap, fix)
-        _lib.check(lib.texgs_preprocess_forward(C.byref(frame), C.byref(inputs), C.byref(geom), stream), "texgs_preprocess_forward")
-        # the one device->host read of a forward (D and K1's geometry fingerprint), in two steps: the copy into pinned memory is issued
-        # here (with K2 behind it unless earlier lists are expected to be shared), the host waits for it in finish() -- immediately when
-        # this is an ordinary forward, or several views later when it was PREFETCHED (prefetch_forward: K1 of a later view issued ahead
-        # of this stream's pending backward, so that its forward never waits for the stream to drain)
-        pin = _pin_take(int(lib.texgs_num_rendered_words(N)))
-        _lib.check(lib.texgs_num_rendered_begin(C.byref(geom), N, pin.data_ptr(), pin.numel(), 0, stream), "texgs_num_rendered_begin")
-        d_ev = torch.cuda.Event()
-        d_ev.record(cur_stream)
-        if not candidate:           # K2 behind the event: the host waits for K1 + the copy only, the device goes on sorting
-            _lib.check(lib.texgs_depth_sort_scan(C.byref(geom), N, stream), "texgs_depth_sort_scan")
 
-    def finish():
-        nonlocal binning, bin_ar, cap
+class _Forward:
+    """One forward in two steps.  begin(): validation, every allocation, K1, the asynchronous copy of K1's partial sums (D and the
+    geometry fingerprint) into pinned memory, an event and -- unless earlier lists are expected to be shared -- K2 behind it.
+    finish(): the forward's one host wait, then K3..K6 or the shared-geometry path -> (outputs, _State).  forward_raw runs both back
+    to back; a prefetched forward sits in _PREFETCH between them, and abandon() is for one dropped from there unfinished."""
+
+    def __init__(self, st, tensors, for_backward, count_bins, lazy):
+        self.st, self.raw, self.flags = st, tensors, (for_backward, count_bins, lazy)
+
+    def key(self):
+        """What identifies a begun forward as THE forward of a later call: settings, every tensor's storage / version / shape, flags."""
+        t = lambda x: None if x is None else (x.data_ptr(), x._version, tuple(x.shape), x.requires_grad)
+        st = self.st
+        return (int(st.image_height), int(st.image_width), float(st.tanfovx), float(st.tanfovy), float(st.scale_modifier), int(st.sh_degree),
+                bool(st.debug), t(st.bg), t(st.viewmatrix), t(st.projmatrix), t(st.campos)) + tuple(t(x) for x in self.raw) + self.flags
+
+    def begin(self):
+        lib, st = _lib.load(), self.st
+        a = self.args = _check_inputs(st, *self.raw)
+        for_backward, count_bins, lazy = self.flags
+        device, N = a.means3D.device, a.N
+        if count_bins is None:
+            count_bins = for_backward
+        self.handoff = bool(for_backward) and not (lazy and unused_streak(device.index) >= 2)
+        self.want_counts = bool(count_bins and for_backward and a.texture is not None and USE_TEX_BINS)
+        H, W = int(st.image_height), int(st.image_width)
+        self.tiles = ((W + _lib.TILE - 1) // _lib.TILE) * ((H + _lib.TILE - 1) // _lib.TILE)
+        cur_stream = torch.cuda.current_stream(device)
+        stream = self.stream = cur_stream.cuda_stream
+        self.keep = list(a[:10])
         with torch.cuda.device(device):
-            d_ev.synchronize()
+            self.frame = _make_frame(st, N, a.K, a.R, device, self.keep)
+            self.inputs = _lib.Inputs(*map(_ptr, a[:10]))
+            i32, f32, u8, n1 = torch.int32, torch.float32, torch.uint8, max(N, 1)
+            # a forward that may share an earlier one's lists: same sizes, same camera tensors -- K1's fingerprint decides
+            self.gints = (N, H, W, a.R if a.texture is not None else 0, float(st.tanfovx), float(st.tanfovy), float(st.scale_modifier),
+                          a.cov3D_precomp is not None)
+            self.cam_key = tuple((t.data_ptr(), t._version) for t in (st.viewmatrix, st.projmatrix, st.campos))
+            gkey = self.gkey = (device.index, int(stream))
+            entry = _GEOM.get(gkey) if GEOM_CACHE else None
+            if entry is not None and not (entry.ints == self.gints and entry.cam_key == self.cam_key):
+                del _GEOM[gkey]         # another view / size: the old lists cannot be shared any more -- let go of their arenas before this
+                entry = None            # forward allocates its own (they stay alive only while a state that shares them does)
+            self.entry = entry          # the candidate to share lists with; None: this forward builds its own
+            # Everything the kernels keep between forward and backward lives in TWO allocations (one sized by N / the image, one by
+            # the instance capacity): ~20 separate torch.empty calls were ~0.1 ms of host time per view.  Tensor views of the
+            # pieces are made on demand (tests, diagnostics).
+            scan_bytes = lib.texgs_scan_temp_bytes(N)
+            fix = self.fix = _Arena(device)
+            fix.add("rec", (n1, _lib.REC_TEST_FLOATS), f32)          # test records: xy, conic, opacity, cull aids
+            fix.add("rec_shade", (n1, _lib.REC_SHADE_FLOATS), f32)
+            fix.add("depth", (n1,), f32)
+            fix.add("rect", (n1, 2), i32)
+            fix.add("tiles_touched", (n1,), i32)
+            fix.add("offsets", (n1,), i32)
+            fix.add("scan_temp", (scan_bytes,), u8)
+            fix.add("final_T", (H, W), f32)
+            fix.add("n_contrib", (H, W), i32)
+            if entry is None:
+                self._add_lists(fix)
+            fix.commit()
+            radii = torch.empty(N, dtype=i32, device=device)          # K1 writes every entry (0 for culled)
+            self.geom = _lib.Geom(fix.ptr("rec"), fix.ptr("rec_shade"), fix.ptr("depth"), _ptr(radii), fix.ptr("rect"),
+                                  fix.ptr("tiles_touched"), fix.ptr("offsets"), fix.ptr("scan_temp"), scan_bytes)
+            # everything is allocated BEFORE the one device->host sync, the D-sized buffers from a capacity hint
+            # (largest D seen on this device x 1.25): K1 -> sync (K2 runs meanwhile) -> K3..K6 with little host work between
+            self.outs = (torch.empty(3, H, W, dtype=f32, device=device), torch.empty(1, H, W, dtype=f32, device=device),
+                         torch.empty(3, H, W, dtype=f32, device=device), torch.empty(1, H, W, dtype=f32, device=device), radii)
+            self.img = _lib.Image(*map(_ptr, self.outs[:4]), fix.ptr("final_T"), fix.ptr("n_contrib"), None, None, None, None, None)
+            self.hint_key = (device.index, N, H, W)
+            self.cap = _CAPACITY_HINT.get(self.hint_key, max(4 * N, 1024))
+            self.binning = self.bin_ar = None
+            if entry is None:
+                self._alloc_bin(self.cap, fix)
+            refs = self.refs = [C.byref(x) for x in (self.frame, self.inputs, self.geom)]
+            _lib.check(lib.texgs_preprocess_forward(*refs, stream), "texgs_preprocess_forward")
+            # the one device->host read of a forward, in two steps: the copy into pinned memory is issued here, finish() waits for it
+            pin = self.pin = _pin_take(int(lib.texgs_num_rendered_words(N)))
+            _lib.check(lib.texgs_num_rendered_begin(refs[2], N, pin.data_ptr(), pin.numel(), 0, stream), "texgs_num_rendered_begin")
+            self.d_ev = torch.cuda.Event()
+            self.d_ev.record(cur_stream)
+            if entry is None:           # K2 behind the event: the host waits for K1 + the copy only, the device goes on sorting
+                _lib.check(lib.texgs_depth_sort_scan(refs[2], N, stream), "texgs_depth_sort_scan")
+        return self
+
+    def _add_lists(self, ar):           # per-tile pieces of the lists (a candidate adds them only if it has to build lists after all)
+        ar.add("ranges", (self.tiles, 2), torch.int32)              # zero-filled by K3
+        ar.add("tile_order", (self.tiles,), torch.int32)
+        if self.handoff:
+            _add_handoff(ar, None, self.tiles, self.args.R, self.want_counts)
+
+    def _alloc_bin(self, cap, lists_ar):
+        """The arena sized by the instance capacity; `lists_ar`: where the per-tile pieces are (None: nowhere yet -- they go in here too)."""
+        c1, tiles = max(cap, 1), self.tiles
+        sort_bytes = _lib.load().texgs_sort_temp_bytes(cap, tiles)
+        ar = self.bin_ar = _Arena(self.fix.device)
+        ar.add("keys_unsorted", (c1,), torch.int64)
+        ar.add("keys_sorted", (c1,), torch.int64)
+        ar.add("point_list", (c1,), torch.int32)
+        ar.add("sort_temp", (sort_bytes,), torch.uint8)
+        if lists_ar is None:
+            self._add_lists(ar)
+        if self.handoff:
+            _add_handoff(ar, cap, None, self.args.R, self.want_counts)
+        ar.commit()
+        la = lists_ar if lists_ar is not None else ar
+        self.binning = _lib.Binning(0, ar.ptr("keys_unsorted"), ar.ptr("keys_sorted"), ar.ptr("point_list"), la.ptr("ranges"),
+                                    la.ptr("tile_order"), ar.ptr("sort_temp"), sort_bytes)
+        for n in _HANDOFF:
+            setattr(self.img, n, (ar if n in ar.specs else la).ptr(n))
+
+    def finish(self):
+        lib, a, img, entry, refs = _lib.load(), self.args, self.img, self.entry, self.refs
+        for_backward, _, lazy = self.flags
+        stream, cap, pin = self.stream, self.cap, self.pin
+        with torch.cuda.device(a.means3D.device):
+            self.d_ev.synchronize()
             d_host, fp_host = C.c_uint32(0), C.c_uint64(0)
-            _lib.check(lib.texgs_num_rendered_reduce(pin.data_ptr(), N, C.byref(d_host), C.byref(fp_host)), "texgs_num_rendered_reduce")
+            _lib.check(lib.texgs_num_rendered_reduce(pin.data_ptr(), a.N, C.byref(d_host), C.byref(fp_host)), "texgs_num_rendered_reduce")
             _pin_give(pin)
             D, fp = int(d_host.value), int(fp_host.value)
-            shared = None
-            if candidate and fp == entry.fingerprint and D == entry.D:
+            shared = entry is not None and fp == entry.fingerprint and D == entry.D
+            if shared:
                 # same geometry as the forward that built `entry`: its lists are this forward's lists; K6 alone, no hand-off work
                 _GEOM_STATS["hits"] += 1
-                shared = entry
-                binning = _lib.Binning(D, *entry.bin)
-                _lib.check(lib.texgs_render_forward(C.byref(frame), C.byref(inputs), C.byref(geom), C.byref(binning), C.byref(img),
-                                                    stream), "texgs_render_forward")
-                if for_backward and entry.handoff and (entry.counts or not want_counts):
+                binning, cap = _lib.Binning(D, *entry.bin), entry.cap
+                _lib.check(lib.texgs_render_forward(*refs, C.byref(binning), C.byref(img), stream), "texgs_render_forward")
+                if for_backward and entry.handoff and (entry.counts or not self.want_counts):
                     img.survivors, img.surv_qmask, img.surv_count = entry.handoff
-                    img.tex_bin_count, img.tex_bin_resv = entry.counts if want_counts else (None, None)
-                cap = entry.cap
+                    img.tex_bin_count, img.tex_bin_resv = entry.counts if self.want_counts else (None, None)
             else:
                 _GEOM_STATS["misses"] += 1
-                if candidate:           # expected to share, cannot: build the lists after all (K2 was not started before the sync)
-                    binning, bin_ar = alloc_bin(max(cap, int(D * 1.25) + 1024), None)
-                    cap = max(cap, int(D * 1.25) + 1024)
-                    _lib.check(lib.texgs_depth_sort_scan(C.byref(geom), N, stream), "texgs_depth_sort_scan")
-                elif D > cap:           # rare: grow
-                    cap = int(D * 1.25) + 1024
-                    binning, bin_ar = alloc_bin(cap, fix)
+                grown = int(D * 1.25) + 1024
+                if entry is not None:       # expected to share, cannot: build the lists after all (K2 was not started before the sync)
+                    cap = max(cap, grown)
+                    self._alloc_bin(cap, None)
+                    _lib.check(lib.texgs_depth_sort_scan(refs[2], a.N, stream), "texgs_depth_sort_scan")
+                elif D > cap:               # rare: grow
+                    cap = grown
+                    self._alloc_bin(cap, self.fix)
+                binning = self.binning
                 binning.num_rendered = D
-                _lib.check(lib.texgs_bin_sort_render_forward(C.byref(frame), C.byref(inputs), C.byref(geom), C.byref(binning),
-                                                             C.byref(img), stream), "texgs_bin_sort_render_forward")
-                _CAPACITY_HINT[hint_key] = max(_CAPACITY_HINT.get(hint_key, 0), int(D * 1.25) + 1024)
+                _lib.check(lib.texgs_bin_sort_render_forward(*refs, C.byref(binning), C.byref(img), stream), "texgs_bin_sort_render_forward")
+                _CAPACITY_HINT[self.hint_key] = max(_CAPACITY_HINT.get(self.hint_key, 0), grown)
                 if GEOM_CACHE:
-                    e = _GeomEntry()
-                    e.ints, e.cam_key, e.fingerprint, e.D, e.cap = gints, cam_key, fp, D, cap
-                    e.bin = (binning.keys_unsorted, binning.keys_sorted, binning.point_list, binning.ranges, binning.tile_order,
-                             binning.sort_temp, binning.sort_temp_bytes)
-                    e.arenas = (fix, bin_ar)
-                    e.handoff = (img.survivors, img.surv_qmask, img.surv_count) if handoff else None
-                    e.counts = (img.tex_bin_count, img.tex_bin_resv) if (handoff and img.tex_bin_count) else None
-                    _GEOM[gkey] = e
-        s = _State()
-        s.frame, s.inputs, s.geom, s.bin, s.img = frame, inputs, geom, binning, img
-        s.N, s.K, s.R, s.H, s.W, s.D, s.cap, s.tiles = N, K, R, H, W, D, cap, tiles
-        s.want_counts, s.lazy, s.backward_ran, s.shared_geometry = want_counts, bool(lazy and for_backward), False, shared is not None
-        with _PRED_LOCK:
-            _SERIAL[0] += 1
-            s.serial = _SERIAL[0]
-        arenas = (fix,) + ((bin_ar,) if bin_ar is not None else ()) + (tuple(shared.arenas) if shared is not None else ())
+                    _GEOM[self.gkey] = _GeomEntry(          # (bin: every field of the binning after num_rendered)
+                        self.gints, self.cam_key, fp, D, cap, tuple(getattr(binning, n) for n, _ in _lib.Binning._fields_[1:]),
+                        (self.fix, self.bin_ar), (img.survivors, img.surv_qmask, img.surv_count) if self.handoff else None,
+                        (img.tex_bin_count, img.tex_bin_resv) if (self.handoff and img.tex_bin_count) else None)
+        arenas = (self.fix,) + ((self.bin_ar,) if self.bin_ar is not None else ()) + (tuple(entry.arenas) if shared else ())
         # (NOT the output tensors: autograd hangs its node on them, the node holds this state -- a cycle that kept every dropped
         #  graph's buffers alive until the garbage collector ran)
-        s.tensors = _Tensors(arenas, keep=keep, radii=radii)
-        if img.survivors is None:           # no hand-off in this state (forward-only call, lazy mode, or a shared entry without one)
-            s.tensors["survivors"] = None
-            s.tensors["surv_qmask"] = None
-            s.tensors["surv_count"] = None
-        if img.tex_bin_count is None:
-            s.tensors["tex_bin_count"] = None
-        s.tensors["for_backward"] = bool(for_backward)
-        return (out_color, out_depth, out_norm, out_alpha, radii), s
+        tensors = _Tensors(arenas, keep=self.keep, radii=self.outs[4], for_backward=bool(for_backward))
+        for n in _HANDOFF:          # no hand-off in this state (forward-only call, lazy mode, or a shared entry without one)
+            if getattr(img, n) is None:
+                tensors[n] = None
+        return self.outs, _State(self.frame, self.inputs, self.geom, binning, img, tensors, a, D, cap, self.tiles, self.want_counts,
+                                 bool(lazy and for_backward), shared)
 
-    if _begin_only:
-        return finish
-    return finish()
+    def abandon(self):
+        """A begun forward that will never be finished: its pinned block may go back to the pool only when the copy into it has landed."""
+        self.d_ev.synchronize()
+        _pin_give(self.pin)
+
+
+def _gpu_only(device):
+    _lib.load()
+    if device.type != "cuda":
+        raise RuntimeError("the textured rasterizer runs on an AMD GPU (torch device 'cuda' = HIP); "
+                           f"got tensors on {device}. There is no CPU fallback.")
+
+
+def prefetch_forward(st, means3D, shs, opacities, scales, rotations, uvs, gradient_uvs, texture, color_offset=None,
+                     for_backward=True, cov3D_precomp=None, count_bins=None, lazy=False):
+    """Begin a forward now -- K1, the asynchronous D readback, K2 -- on the current stream; a later forward_raw / GaussianRasterizer
+    call on this stream with the same arguments (same tensor storages and versions, same settings, same flags) finishes it without
+    waiting for the device.  At most four forwards are kept pending per stream (older ones are dropped: their K1 was wasted, and the
+    host waits for it once).  Returns nothing."""
+    device = means3D.device
+    _gpu_only(device)
+    fwd = _Forward(st, (means3D, shs, opacities, scales, rotations, uvs, gradient_uvs, texture, color_offset, cov3D_precomp),
+                   for_backward, count_bins, lazy).begin()
+    lst = _PREFETCH.setdefault((device.index, int(torch.cuda.current_stream(device).cuda_stream)), [])
+    lst.append((fwd.key(), fwd))
+    for _, old in lst[:-4]:
+        old.abandon()
+    del lst[:-4]
+
+
+def forward_raw(st, means3D, shs, opacities, scales, rotations, uvs, gradient_uvs, texture, color_offset=None,
+                for_backward=True, cov3D_precomp=None, count_bins=None, lazy=False):
+    """Run K1..K6.  Returns (outputs, state).  No autograd here.
+
+    `lazy` (the autograd path sets it): the hand-off may be left to the backward (the predictor above: unused_streak).
+
+    `for_backward`: K6 leaves the per-block survivor lists its backward replays.  `count_bins` (default: for_backward and
+    there is a texture): K6 also counts the texture-gradient footprints per texture bin (the exact list sizes of
+    backward_raw's binned texture gradient); a caller that will not ask for dL/dtexture saves that work.
+    `texture=None`: the untextured surface (diff_gauss, render/render.py:75-84): uvs / gradient_uvs may be None too.
+    `cov3D_precomp` f32[N,6] (untextured surface only): used instead of scales / rotations."""
+    _gpu_only(means3D.device)
+    fwd = _Forward(st, (means3D, shs, opacities, scales, rotations, uvs, gradient_uvs, texture, color_offset, cov3D_precomp),
+                   for_backward, count_bins, lazy)
+    # was this very forward begun earlier (prefetch_forward)?  Then K1 ran long ago: finish that one
+    pend = _prefetch_take(means3D.device, fwd.key()) if _PREFETCH else None
+    return (pend or fwd.begin()).finish()
 
 
 def _late_handoff(s: _State):
-    """The forward left no survivor lists (LAZY_HANDOFF, or lists shared from a forward that had none): produce them now with one
+    """The forward left no survivor lists (lazy mode, or lists shared from a forward that had none): produce them now with one
     more K6 on the state's lists -- outputs into scratch (bit-identical to the forward's, which stay untouched)."""
     lib = _lib.load()
-    device = s.tensors["keep"][0].device
+    device = s.args.means3D.device
     stream = torch.cuda.current_stream(device).cuda_stream
-    i32, f32 = torch.int32, torch.float32
     ar = _Arena(device)
-    ar.add("survivors", (4 * max(s.cap, 1), 2), i32)
-    ar.add("surv_qmask", (4 * max(s.cap, 1),), torch.int16)
-    ar.add("surv_count", (4 * s.tiles,), i32)
-    if s.want_counts:
-        ar.add("tex_bin_count", (2 * int(lib.texgs_tex_bin_count(s.R)),), i32)
-        ar.add("tex_bin_resv", (4 * s.tiles, _lib.RESV_WORDS), i32)
-    ar.add("scratch_out", (8, s.H, s.W), f32)
-    ar.add("final_T", (s.H, s.W), f32)
-    ar.add("n_contrib", (s.H, s.W), i32)
+    _add_handoff(ar, s.cap, s.tiles, s.R, s.want_counts)
+    ar.add("scratch_out", (8, s.H, s.W), torch.float32)
+    ar.add("final_T", (s.H, s.W), torch.float32)
+    ar.add("n_contrib", (s.H, s.W), torch.int32)
     ar.commit()
     so = ar.ptr("scratch_out")
     hw = 4 * s.H * s.W
-    img = _lib.Image(so, so + 3 * hw, so + 4 * hw, so + 7 * hw, ar.ptr("final_T"), ar.ptr("n_contrib"), ar.ptr("tex_bin_count"),
-                     ar.ptr("survivors"), ar.ptr("surv_qmask"), ar.ptr("surv_count"), ar.ptr("tex_bin_resv"))
+    img = _lib.Image(so, so + 3 * hw, so + 4 * hw, so + 7 * hw, ar.ptr("final_T"), ar.ptr("n_contrib"), *(ar.ptr(n) for n in _HANDOFF))
     _lib.check(lib.texgs_render_forward(C.byref(s.frame), C.byref(s.inputs), C.byref(s.geom), C.byref(s.bin), C.byref(img), stream),
                "texgs_render_forward (late hand-off)")
-    s.img.survivors, s.img.surv_qmask, s.img.surv_count = img.survivors, img.surv_qmask, img.surv_count
-    s.img.tex_bin_count, s.img.tex_bin_resv = img.tex_bin_count, img.tex_bin_resv
     s.tensors._arenas = tuple(s.tensors._arenas) + (ar,)
-    for n in ("survivors", "surv_qmask", "surv_count", "tex_bin_count", "tex_bin_resv"):
+    for n in _HANDOFF:
+        setattr(s.img, n, ar.ptr(n))
         s.tensors.pop(n, None)
-    if not s.want_counts:
-        s.tensors["tex_bin_count"] = None
+        if n not in ar.specs:
+            s.tensors[n] = None
     _GEOM_STATS["late_handoffs"] += 1
 
 
-_ITEMSIZE = {torch.float32: 4, torch.int32: 4, torch.int64: 8, torch.int16: 2, torch.uint8: 1, torch.float64: 8}
-
-
-class _Arena:
-    """One device allocation carved into named, 256-byte-aligned pieces."""
-
-    def __init__(self, device):
-        self.device, self.specs, self.size, self.buf = device, {}, 0, None
-
-    def add(self, name, shape, dtype):
-        off = (self.size + 255) & ~255
-        self.specs[name] = (off, tuple(shape), dtype)
-        self.size = off + math.prod(shape) * _ITEMSIZE[dtype]
-
-    def commit(self):
-        self.buf = torch.empty(max(self.size, 1), dtype=torch.uint8, device=self.device)
-
-    def ptr(self, name):
-        return self.buf.data_ptr() + self.specs[name][0] if name in self.specs else None
-
-    def view(self, name):
-        off, shape, dtype = self.specs[name]
-        n = math.prod(shape) * _ITEMSIZE[dtype]
-        return self.buf[off:off + n].view(dtype).view(shape)
-
-
-class _Tensors(dict):
-    """What a forward leaves behind, by name: real tensors (inputs kept alive, outputs) plus views into the arenas, made on
-    first access.  A name that was not allocated (e.g. the survivor lists of a forward-only call) reads as None."""
-
-    def __init__(self, arenas, **real):
-        super().__init__(**real)
-        self._arenas = arenas
-
-    def __missing__(self, name):
-        for ar in self._arenas:
-            if name in ar.specs:
-                self[name] = v = ar.view(name)
-                return v
-        self[name] = None
-        return None
-
-    def get(self, name, default=None):
-        v = self[name]
-        return default if v is None else v
+def _plan_outputs(N, K, textured, has_cov, has_coff, want, sinks, device):
+    """Where K8 writes the per-Gaussian gradients -> (outs, mask, returned).  `outs`: name -> tensor, the sink where there is one, else
+    a view of ONE fresh allocation; `mask`: the _ACC_BITS of the sinks (K8 adds into those); `returned`: what backward_raw hands back
+    under each name (None for an output that went into a sink).  Nothing is planned without WANT_GAUSSIANS."""
+    shapes = {}
+    if want & _lib.WANT_GAUSSIANS:
+        shapes = dict(means3D=(N, 3), means2D=(N, 3), opacities=(N, 1))
+        if has_cov:
+            shapes["cov3D"] = (N, 6)
+        else:
+            shapes.update(scales=(N, 3), rotations=(N, 4))
+        if textured:
+            shapes["uvs"] = (N, 3)
+        if K > 0:
+            shapes["shs"] = (N, K, 3)
+        if has_coff:
+            shapes["color_offset"] = (N, 3)
+    fresh = [n for n in shapes if n not in sinks]
+    sizes = [math.prod(shapes[n]) for n in fresh]
+    flat = torch.empty(sum(sizes), dtype=torch.float32, device=device).split(sizes) if fresh else ()
+    outs, mask = {n: v.view(shapes[n]) for n, v in zip(fresh, flat)}, 0
+    for n in shapes.keys() - set(fresh):
+        t = outs[n] = sinks[n]
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == math.prod(shapes[n]), n
+        mask |= _ACC_BITS[n]
+    return outs, mask, {n: (None if n in sinks else outs[n]) for n in shapes}
 
 
 def backward_raw(s: _State, dL_dcolor, dL_ddepth, dL_dnorm, dL_dalpha, sinks=None, before_accumulate=None,
@@ -619,13 +654,12 @@ def backward_raw(s: _State, dL_dcolor, dL_ddepth, dL_dnorm, dL_dalpha, sinks=Non
     lib = _lib.load()
     if not s.tensors["for_backward"]:
         raise RuntimeError("this forward ran with for_backward=False (no survivor lists were kept): its backward cannot run")
-    means3D = s.tensors["keep"][0]
-    device = means3D.device
+    a = s.args
+    device = a.means3D.device
     f32 = dict(dtype=torch.float32, device=device)
-    N, K, R = s.N, s.K, s.R
+    N, R = s.N, s.R
     stream = torch.cuda.current_stream(device).cuda_stream
-    textured = s.tensors["keep"][7] is not None
-    has_cov = s.tensors["keep"][9] is not None
+    textured = a.texture is not None
     want &= _lib.WANT_ALL if textured else _lib.WANT_GAUSSIANS
     want_g, want_t = bool(want & _lib.WANT_GAUSSIANS), bool(want & _lib.WANT_TEXTURE)
     if not want:
@@ -637,8 +671,7 @@ def backward_raw(s: _State, dL_dcolor, dL_ddepth, dL_dnorm, dL_dalpha, sinks=Non
         t = t.to(torch.float32).contiguous()
         assert tuple(t.shape) == shape, (tuple(t.shape), shape)
         return t
-    H, W = s.H, s.W
-    dc, dd, dn, da = g(dL_dcolor, (3, H, W)), g(dL_ddepth, (1, H, W)), g(dL_dnorm, (3, H, W)), g(dL_dalpha, (1, H, W))
+    dc, dd, dn, da = g(dL_dcolor, (3, s.H, s.W)), g(dL_ddepth, (1, s.H, s.W)), g(dL_dnorm, (3, s.H, s.W)), g(dL_dalpha, (1, s.H, s.W))
     with torch.cuda.device(device):
         if s.img.survivors is None:
             _late_handoff(s)
@@ -647,45 +680,14 @@ def backward_raw(s: _State, dL_dcolor, dL_ddepth, dL_dnorm, dL_dalpha, sinks=Non
             with _PRED_LOCK:
                 _LAST_DIFFERENTIATED[device.index] = max(_LAST_DIFFERENTIATED.get(device.index, -1), s.serial)
         skey = (device.index, int(stream))
-        sc = _SCRATCH.pop(skey, None) or _StreamScratch()     # re-cached only after a successful call (an exception drops it)
-        acc = None
-        if want_g:
-            if sc.acc is None or sc.acc.shape[0] < max(N, 1):
-                sc.acc = torch.zeros(max(N, 1), _lib.ACC_FLOATS, **f32)
-            acc = sc.acc
+        sc = _SCRATCH.pop(skey, None) or SimpleNamespace(acc=None, bins=None)     # re-cached only after success (an exception drops it)
+        if want_g and (sc.acc is None or sc.acc.shape[0] < max(N, 1)):
+            sc.acc = torch.zeros(max(N, 1), _lib.ACC_FLOATS, **f32)
+        acc = sc.acc if want_g else None
         sinks = sinks or {}
-        has_coff = s.tensors["keep"][8] is not None
-        shapes = {}
-        if want_g:
-            shapes = dict(means3D=(N, 3), means2D=(N, 3), opacities=(N, 1))
-            if has_cov:
-                shapes["cov3D"] = (N, 6)
-            else:
-                shapes.update(scales=(N, 3), rotations=(N, 4))
-            if textured:
-                shapes["uvs"] = (N, 3)
-            if K > 0:
-                shapes["shs"] = (N, K, 3)
-            if has_coff:
-                shapes["color_offset"] = (N, 3)
-        # one allocation for every per-Gaussian output without a sink
-        fresh = [n for n in shapes if n not in sinks]
-        flat = torch.empty(sum(math.prod(shapes[n]) for n in fresh), **f32) if fresh else None
-        outs, off, mask = {}, 0, 0
-        for n, shp in shapes.items():
-            if n in sinks:
-                t = sinks[n]
-                assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == math.prod(shp), n
-                outs[n] = t
-                mask |= _ACC_BITS[n]
-            else:
-                cnt = math.prod(shp)
-                outs[n] = flat[off:off + cnt].view(shp)
-                off += cnt
+        outs, mask, res = _plan_outputs(N, s.K, textured, a.cov3D_precomp is not None, a.color_offset is not None, want, sinks, device)
         tex_sink = sinks.get("texture") if want_t else None
-        d_tex = None
-        if want_t:
-            d_tex = tex_sink if tex_sink is not None else torch.zeros(6, R, R, 3, **f32)
+        d_tex = (tex_sink if tex_sink is not None else torch.zeros(6, R, R, 3, **f32)) if want_t else None
         bins = None
         if want_t and USE_TEX_BINS and s.tensors.get("tex_bin_count") is not None:
             bins = sc.bins if (sc.bins is not None and sc.bins.R == R) else _TexBins(lib, device, R)
@@ -696,24 +698,21 @@ def backward_raw(s: _State, dL_dcolor, dL_ddepth, dL_dnorm, dL_dalpha, sinks=Non
                            _ptr(outs.get("uvs")), _ptr(d_tex), _ptr(outs.get("color_offset")), _ptr(outs.get("cov3D")), want,
                            _ptr(bins.rec) if bins else None, _ptr(bins.cursor) if bins else None,
                            _ptr(bins.base) if bins else None, bins.cap if bins else 0, mask)
+        refs = [C.byref(x) for x in (s.frame, s.inputs, s.geom, s.bin, s.img, grads)]
         if before_accumulate is None:
-            _lib.check(lib.texgs_backward(C.byref(s.frame), C.byref(s.inputs), C.byref(s.geom), C.byref(s.bin),
-                                          C.byref(s.img), C.byref(grads), stream), "texgs_backward")
+            _lib.check(lib.texgs_backward(*refs, stream), "texgs_backward")
         else:
-            _lib.check(lib.texgs_backward_render(C.byref(s.frame), C.byref(s.inputs), C.byref(s.geom), C.byref(s.bin),
-                                                 C.byref(s.img), C.byref(grads), stream), "texgs_backward_render")
+            _lib.check(lib.texgs_backward_render(*refs, stream), "texgs_backward_render")
             before_accumulate()
-            _lib.check(lib.texgs_backward_preprocess(C.byref(s.frame), C.byref(s.inputs), C.byref(s.geom),
-                                                     C.byref(grads), stream), "texgs_backward_preprocess")
+            _lib.check(lib.texgs_backward_preprocess(*refs[:3], refs[5], stream), "texgs_backward_preprocess")
     if bins is not None:
         bins.after_call()
         sc.bins = bins
     _SCRATCH[skey] = sc
-    res = {n: (None if n in sinks else outs[n]) for n in shapes}
     s.tensors["d_color_offset"] = res.get("color_offset")
     s.tensors["d_cov3D"] = res.get("cov3D")
-    return (res.get("means3D"), res.get("means2D"), res.get("shs"), res.get("opacities"), res.get("scales"), res.get("rotations"),
-            res.get("uvs"), None if tex_sink is not None else d_tex)
+    return tuple(res.get(n) for n in ("means3D", "means2D", "shs", "opacities", "scales", "rotations", "uvs")) \
+        + (None if tex_sink is not None else d_tex,)
 
 
 def _leaf_grad_sink(t):
