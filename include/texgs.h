@@ -437,6 +437,71 @@ int texgs_cube_sample_backward(const float* tex, int32_t R, int32_t C, const flo
 int texgs_cube_sample_nearest_backward(int32_t R, int32_t C, const float* dirs, int32_t N, const float* g_out, float* d_tex,
                                        void* stream);
 
+/* ---- stage-1 density control (additive in v19; csrc/density.hip; models/gaussian3d.py:200-350, :424-462) ---------------------------
+ * The version stays 19: nothing that existed changes.  texgs_abi_version() therefore does not tell a v19 library with these entries
+ * from one without; a loader finds out by looking the symbols up (texgs/_lib.py EXPORTS does, and asks for a rebuild).
+ * Per-step statistics, one launch, nothing read back.  grad f32[n, 3], radii i32[n]; for every i with radii[i] > 0:
+ *   accum[i] += sqrtf(gx*gx + gy*gy)  (fp32, no FMA, correctly rounded);  denom[i] += 1;  max_radii[i] = max(max_radii[i], (float)radii[i]). */
+int texgs_density_stats(const float* grad, const int32_t* radii, int32_t n, float* accum, float* denom, float* max_radii, void* stream);
+
+/* The plan of one densify_and_prune over the n Gaussians it starts from.  Per Gaussian: g = accum / denom (NaN -> 0),
+ * s = expf(scaling) per axis, m = max s, o = 1 / (1 + expf(-opacity)), gone = o < min_opacity || (use_big && m > big_scale).
+ *   densify != 0:  clone = sqrtf(g*g) >= max_grad && m <= dense_scale;   split = g >= max_grad && m > dense_scale
+ *   split:      SPLIT; the pair of children has scaling c = logf(s / 1.6f) and survives (CHILD) unless
+ *               o < min_opacity || (use_big && max expf(c) > big_scale); the parent never survives
+ *   otherwise:  KEEP unless gone; CLONE when cloned, CLONE_KEPT when the clone survives (it shares its parent's fate)
+ * action u8[n]: the bits below.  rank i32[4, n]: the EXCLUSIVE prefix counts over i of KEEP, CLONE_KEPT, SPLIT, CHILD;
+ * totals u32[4]: their sums (device memory; the caller reads them back to size the outputs).  Three launches (per-tile counts, one
+ * block scans the tiles, per-tile scan plus offset), no atomics.  temp: texgs_density_plan_temp_bytes(n).  n = 0: totals zeroed. */
+#define TEXGS_DENSITY_KEEP       1
+#define TEXGS_DENSITY_CLONE      2
+#define TEXGS_DENSITY_CLONE_KEPT 4
+#define TEXGS_DENSITY_SPLIT      8
+#define TEXGS_DENSITY_CHILD      16
+typedef struct {
+    const float* accum;       /* f32[n] */
+    const float* denom;       /* f32[n] */
+    const float* scaling;     /* f32[n, 3] raw (log) */
+    const float* opacity;     /* f32[n] raw (logit) */
+    int32_t n;
+    float max_grad, min_opacity, dense_scale, big_scale;
+    int32_t densify, use_big;
+} TexGSDensityPlan;
+size_t texgs_density_plan_temp_bytes(int32_t n);
+int texgs_density_plan(const TexGSDensityPlan* plan, uint8_t* action, int32_t* rank, uint32_t* totals, void* temp, void* stream);
+
+/* The move: every output row of every listed tensor is written exactly once, in one launch.  Output row order: KEEP originals
+ * (row rank[0][i]), CLONE_KEPT clones (n_kept + rank[1][i]), first children (n_kept + n_clone + rank[3][i]), second children
+ * (+ n_child).  src f32[n, width] -> dst f32[n_kept + n_clone + 2 n_child, width] by kind:
+ *   COPY     every output row of i is a copy of src row i
+ *   MOMENT   the kept original's row is a copy; clones and children are 0
+ *   SCALING  as COPY, children get logf(expf(src) / 1.6f)
+ *   XYZ      as COPY (width 3), child c of the j-th split parent (j = rank[2][i]) gets
+ *            src + R(q / |q|) (s * eps), eps = noise row c n_split + j, R as utils/general.py:87-108, s = expf(scaling row i) */
+#define TEXGS_DENSITY_ROW_COPY    0
+#define TEXGS_DENSITY_ROW_MOMENT  1
+#define TEXGS_DENSITY_ROW_SCALING 2
+#define TEXGS_DENSITY_ROW_XYZ     3
+#define TEXGS_DENSITY_MAX_ROWS    24
+typedef struct {
+    const float* src;
+    float* dst;
+    int32_t width;
+    int32_t kind;
+} TexGSDensityRow;
+typedef struct {
+    TexGSDensityRow row[TEXGS_DENSITY_MAX_ROWS];
+    int32_t rows;
+    int32_t n;
+    const uint8_t* action;    /* u8[n] of texgs_density_plan */
+    const int32_t* rank;      /* i32[4, n] */
+    int32_t n_kept, n_clone, n_split, n_child;      /* totals of the plan */
+    const float* scaling;     /* f32[n, 3] and */
+    const float* rotation;    /* f32[n, 4] of the originals, and */
+    const float* noise;       /* f32[2 n_split, 3]: read only by an XYZ row with n_child > 0 */
+} TexGSDensityMove;
+int texgs_density_move(const TexGSDensityMove* move, void* stream);
+
 /* Hardware self-test of the wave64 cross-lane primitives the backward's reductions use (csrc/wave_ops.h: DPP lane^4 /
  * lane^8 exchanges, permlane16/32 swaps, both transposing butterflies).  seed: f32[128] device; out: f32[576] device,
  * nine blocks of 64 differences against the __shfl_xor formulation -- all exactly 0 on gfx950. */

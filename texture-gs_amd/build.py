@@ -2,7 +2,7 @@
 
 Objects are rebuilt only when their sources are newer.  preprocess.hip is built with -ffp-contract=off (its
 fp32 operation order is part of the bit-exact key/rect/radius contract) and so is points.hip (its squared distance is
-compared bit for bit); the render kernels allow contraction
+compared bit for bit) and density.hip (its per-step statistics likewise); the render kernels allow contraction
 and use hardware fp32 atomics (-munsafe-fp-atomics).
 """
 import os
@@ -31,6 +31,7 @@ UNITS = {
     "uvmap.hip": ["-munsafe-fp-atomics"],
     "points.hip": ["-ffp-contract=off"],      # its squared distance is a bit-exact contract: no fused multiply-add
     "cubetex.hip": ["-munsafe-fp-atomics"],   # the texture gradient's scatter: hardware fp32 atomic adds
+    "density.hip": ["-ffp-contract=off"],     # the per-step statistics are a bit-exact contract: x*x + y*y with separate roundings
     "abi.hip": [],
 }
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "wave_ops.h"), os.path.join(CSRC, "render_bwd_body.h"),

@@ -500,6 +500,48 @@ int texgs_cube_sample_nearest_backward(int32_t R, int32_t C, const float* dirs, 
     return 0;
 }
 
+int texgs_density_stats(const float* grad, const int32_t* radii, int32_t n, float* accum, float* denom, float* max_radii, void* stream) {
+    if (n < 0) return fail_msg("n < 0");
+    if (n > 0 && (!grad || !radii || !accum || !denom || !max_radii)) return fail_msg("NULL argument");
+    if (int r = launch_density_stats(grad, radii, n, accum, denom, max_radii, (hipStream_t)stream)) return fail("density_stats", (hipError_t)r);
+    return 0;
+}
+
+size_t texgs_density_plan_temp_bytes(int32_t n) { return density_plan_temp_bytes(n); }
+
+int texgs_density_plan(const TexGSDensityPlan* plan, uint8_t* action, int32_t* rank, uint32_t* totals, void* temp, void* stream) {
+    if (!plan || !totals) return fail_msg("NULL argument");
+    if (plan->n < 0) return fail_msg("n < 0");
+    if (plan->n > 0 && (!plan->scaling || !plan->opacity || !action || !rank || !temp)) return fail_msg("NULL argument");
+    if (plan->n > 0 && plan->densify && (!plan->accum || !plan->denom)) return fail_msg("accum and denom are required to densify");
+    if (plan->densify && !(plan->max_grad > 0.0f)) return fail_msg("max_grad must be positive (with 0 the reference splits its own clones)");
+    if (int r = launch_density_plan(plan, action, rank, totals, temp, (hipStream_t)stream)) return fail("density_plan", (hipError_t)r);
+    return 0;
+}
+
+int texgs_density_move(const TexGSDensityMove* m, void* stream) {
+    if (!m) return fail_msg("NULL argument");
+    if (m->n < 0 || m->n_kept < 0 || m->n_clone < 0 || m->n_split < 0 || m->n_child < 0) return fail_msg("negative count");
+    if (m->n_kept > m->n || m->n_clone > m->n || m->n_split > m->n || m->n_child > m->n_split) return fail_msg("totals exceed n");
+    if ((int64_t)m->n_kept + m->n_clone + 2ll * m->n_child >= (1ll << 31)) return fail_msg("the new row count reaches 2^31");
+    if (m->rows < 0 || m->rows > TEXGS_DENSITY_MAX_ROWS) return fail_msg("rows must be in [0, TEXGS_DENSITY_MAX_ROWS]");
+    if (m->n == 0 || m->rows == 0) return 0;
+    if (!m->action || !m->rank) return fail_msg("NULL argument");
+    const bool out_rows = m->n_kept + m->n_clone + m->n_child > 0;
+    for (int d = 0; d < m->rows; ++d) {
+        const TexGSDensityRow& r = m->row[d];
+        if (r.width < 1) return fail_msg("row width < 1");
+        if (r.kind < TEXGS_DENSITY_ROW_COPY || r.kind > TEXGS_DENSITY_ROW_XYZ) return fail_msg("unknown row kind");
+        if (r.kind == TEXGS_DENSITY_ROW_XYZ && r.width != 3) return fail_msg("an XYZ row has width 3");
+        if (!r.src || (out_rows && !r.dst)) return fail_msg("NULL row pointer");
+        if (r.kind == TEXGS_DENSITY_ROW_XYZ && m->n_child > 0 && (!m->scaling || !m->rotation || !m->noise))
+            return fail_msg("an XYZ row with children needs scaling, rotation and noise");
+    }
+    if (!out_rows) return 0;        // everything pruned: there is no row to write
+    if (int r = launch_density_move(m, (hipStream_t)stream)) return fail("density_move", (hipError_t)r);
+    return 0;
+}
+
 int texgs_selftest_waveops(const float* seed128, float* out576, void* stream) {
     if (!seed128 || !out576) return fail_msg("NULL argument");
     launch_selftest_waveops(seed128, out576, (hipStream_t)stream);

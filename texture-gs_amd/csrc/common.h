@@ -107,3 +107,7 @@ int launch_cube_latlong(const float* tex, int R, int C, int H, int W, int tap_ma
 int launch_cube_sample_backward(const float* tex, int R, int C, const float* dirs, int N, const float* g_out, float* d_tex,
                                 float* d_dirs, hipStream_t s);
 int launch_cube_sample_nearest_backward(int R, int C, const float* dirs, int N, const float* g_out, float* d_tex, hipStream_t s);
+int launch_density_stats(const float* grad, const int32_t* radii, int n, float* accum, float* denom, float* max_radii, hipStream_t s);
+size_t density_plan_temp_bytes(int n);
+int launch_density_plan(const TexGSDensityPlan* p, uint8_t* action, int32_t* rank, uint32_t* totals, void* temp, hipStream_t s);
+int launch_density_move(const TexGSDensityMove* m, hipStream_t s);

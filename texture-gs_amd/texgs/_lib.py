@@ -73,6 +73,27 @@ class UVNetGradStruct(C.Structure):
     _fields_ = [(n, _fp) for n in ("dW1", "db1", "dW2", "db2", "dW3", "db3", "dW4", "db4", "dW5", "db5")]
 
 
+DENSITY_KEEP, DENSITY_CLONE, DENSITY_CLONE_KEPT, DENSITY_SPLIT, DENSITY_CHILD = 1, 2, 4, 8, 16      # TEXGS_DENSITY_* action bits
+DENSITY_ROW = {"copy": 0, "moment": 1, "scaling": 2, "xyz": 3}                                      # TEXGS_DENSITY_ROW_*
+DENSITY_MAX_ROWS = 24
+
+
+class DensityPlanStruct(C.Structure):
+    _fields_ = [("accum", _fp), ("denom", _fp), ("scaling", _fp), ("opacity", _fp), ("n", C.c_int32), ("max_grad", C.c_float),
+                ("min_opacity", C.c_float), ("dense_scale", C.c_float), ("big_scale", C.c_float), ("densify", C.c_int32),
+                ("use_big", C.c_int32)]
+
+
+class DensityRowStruct(C.Structure):
+    _fields_ = [("src", _fp), ("dst", _fp), ("width", C.c_int32), ("kind", C.c_int32)]
+
+
+class DensityMoveStruct(C.Structure):
+    _fields_ = [("row", DensityRowStruct * DENSITY_MAX_ROWS), ("rows", C.c_int32), ("n", C.c_int32), ("action", _fp), ("rank", _fp),
+                ("n_kept", C.c_int32), ("n_clone", C.c_int32), ("n_split", C.c_int32), ("n_child", C.c_int32), ("scaling", _fp),
+                ("rotation", _fp), ("noise", _fp)]
+
+
 UV_PRECISION = {"fp32": 0, "bf16x3": 1, "mixed": 2}          # TEXGS_UV_FP32 / _BF16X3 / _MIXED
 
 
@@ -85,7 +106,8 @@ EXPORTS = ["texgs_abi_version", "texgs_build_id", "texgs_last_error", "texgs_sca
            "texgs_hashgrid_levels", "texgs_hashgrid_forward", "texgs_hashgrid_backward_temp_bytes", "texgs_hashgrid_backward",
            "texgs_chamfer_nn_temp_bytes", "texgs_chamfer_nn",
            "texgs_knn3_temp_bytes", "texgs_knn3_mean_dist2", "texgs_fps_temp_bytes", "texgs_farthest_points",
-           "texgs_cube_sample", "texgs_cube_latlong", "texgs_cube_sample_backward", "texgs_cube_sample_nearest_backward"]
+           "texgs_cube_sample", "texgs_cube_latlong", "texgs_cube_sample_backward", "texgs_cube_sample_nearest_backward",
+           "texgs_density_stats", "texgs_density_plan_temp_bytes", "texgs_density_plan", "texgs_density_move"]
 KERNEL_NAMES = ["preprocess_fwd", "scan", "duplicate", "sort", "ranges", "render_fwd", "render_bwd", "preprocess_bwd",
                 "texgrad_reduce"]
 
@@ -179,6 +201,14 @@ def load():
     lib.texgs_cube_sample_backward.restype = C.c_int
     lib.texgs_cube_sample_nearest_backward.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.texgs_cube_sample_nearest_backward.restype = C.c_int
+    lib.texgs_density_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.texgs_density_stats.restype = C.c_int
+    lib.texgs_density_plan_temp_bytes.argtypes = [C.c_int32]
+    lib.texgs_density_plan_temp_bytes.restype = C.c_size_t
+    lib.texgs_density_plan.argtypes = [P(DensityPlanStruct), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.texgs_density_plan.restype = C.c_int
+    lib.texgs_density_move.argtypes = [P(DensityMoveStruct), C.c_void_p]
+    lib.texgs_density_move.restype = C.c_int
     lib.texgs_selftest_waveops.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     lib.texgs_selftest_waveops.restype = C.c_int
     lib.texgs_profile_enable.argtypes = [C.c_int]
