@@ -60,10 +60,9 @@ def geom_losses(norm, gt_norm, gt_image, mask, depth, gt_depth, ln, ls, ld, gamm
     return loss
 
 
-def norm_from_depth(depth, world_view_transform, tanfovx, tanfovy, threshold=1e-2):
-    """losses/norm_reg_loss.py:16-63 restated with slices instead of conv2d filters: back-projection of every pixel with
-    ndc = (2 p + 1) / S - 1, one-sided differences with replicate border, normal = normalise(cross(grad_y, grad_x), eps 1e-6),
-    mask = all four one-sided differences shorter than `threshold`.  Works in the dtype of `depth`."""
+def one_sided_differences(depth, world_view_transform, tanfovx, tanfovy):
+    """losses/norm_reg_loss.py:16-52: back-projection of every pixel with ndc = (2 p + 1) / S - 1 and the four one-sided
+    differences (left, right, up, down; replicate border) of the world-space points, each [3,H,W], in the dtype of `depth`."""
     _, H, W = depth.shape
     dt = depth.dtype
     px = torch.arange(W, dtype=dt).reshape(1, 1, W).expand(1, H, W)
@@ -74,8 +73,15 @@ def norm_from_depth(depth, world_view_transform, tanfovx, tanfovy, threshold=1e-
     xyz = (c2w @ cc.reshape(4, H * W)).reshape(4, H, W)[:3]
     pad = F.pad(xyz.unsqueeze(0), (1, 1, 1, 1), mode="replicate").squeeze(0)
     c = pad[:, 1:-1, 1:-1]
-    gl, gr = c - pad[:, 1:-1, :-2], pad[:, 1:-1, 2:] - c
-    gu, gd = c - pad[:, :-2, 1:-1], pad[:, 2:, 1:-1] - c
+    return c - pad[:, 1:-1, :-2], pad[:, 1:-1, 2:] - c, c - pad[:, :-2, 1:-1], pad[:, 2:, 1:-1] - c
+
+
+def norm_from_depth(depth, world_view_transform, tanfovx, tanfovy, threshold=1e-2):
+    """losses/norm_reg_loss.py:16-63 restated with slices instead of conv2d filters: one-sided differences of the back-projected
+    points, normal = normalise(cross(grad_y, grad_x), eps 1e-6), mask = all four one-sided differences shorter than `threshold`.
+    Works in the dtype of `depth`."""
+    dt = depth.dtype
+    gl, gr, gu, gd = one_sided_differences(depth, world_view_transform, tanfovx, tanfovy)
     gx, gy = (gr + gl) / 2, (gd + gu) / 2
     mask = ((gl.norm(dim=0, keepdim=True) < threshold) & (gr.norm(dim=0, keepdim=True) < threshold)
             & (gu.norm(dim=0, keepdim=True) < threshold) & (gd.norm(dim=0, keepdim=True) < threshold))

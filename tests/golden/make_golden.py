@@ -13,6 +13,11 @@ no source) travel to the GPU box, the reference does not.
   geom_losses.npz  losses/norm_reg_loss.py norm_loss, losses/smooth_loss.py smooth_loss and losses/pixelwise_loss.py l1_loss
                combined as models/texture_gaussian3d.py:347-368 combines them (lambda_norm 0.1, lambda_norm_smooth 0.5 of
                configs/texture_gaussian3d.yaml, plus a depth term), values AND autograd gradients w.r.t. norm / depth
+  loss_edges.npz  the same reference functions (l1_loss, ssim_loss, norm_loss, smooth_loss) and their autograd at the shapes and
+               values where the fused kernels take other paths: images smaller than the 11-tap SSIM window (1x1, 1x9, 9x1, 5x7),
+               one partial-tile case (17x31), exact ties (img == gt, alpha == gt_alpha, depth == gt_depth, piecewise-constant
+               normals with a zero region), img = gt + 1e-3 noise, a fractional mask, gamma 0.1 and 0.01; every term alone with
+               its own gradient (dimg for lambda_dssim 0 / 1 / 0.2)
   norm_from_depth.npz  losses/norm_reg_loss.py norm_from_depth (pseudo-normal + mask of a depth map) and norm_reg_loss with its
                autograd gradient w.r.t. the predicted normal, two cameras from utils/graphics.py getWorld2View2
   host_terms.npz  losses/zero_one_loss.py zero_one_loss (value + autograd gradient, both clamps hit) and
@@ -157,6 +162,79 @@ def geom_losses():
         # mask = None variant of the smoothness term is not reachable in the reference (mask.float() on None): skipped
     out.update(ln=0.1, ls=0.5, ld=0.3, gamma=0.1)
     np.savez_compressed(os.path.join(HERE, "geom_losses.npz"), **out)
+
+
+LOSS_EDGE_RGB = {"1x1": "noise", "1x9": "noise", "9x1": "noise", "5x7": "ties", "17x31": "near"}
+LOSS_EDGE_GEOM = ["1x1", "1x9", "9x1", "2x2", "17x15"]
+
+
+def loss_edges():
+    """The reference's loss functions in float32, as the reference runs them, at the edge shapes and values listed in the module
+    docstring.  Arrays only; every term separately with its own autograd gradient."""
+    sys.path.insert(0, REF)
+    from losses.pixelwise_loss import l1_loss
+    from losses.ssim_loss import ssim_loss
+    from losses.norm_reg_loss import norm_loss
+    from losses.smooth_loss import smooth_loss
+    g = torch.Generator().manual_seed(33)
+    f32, f64 = (lambda t: t.detach().numpy().astype(np.float32)), (lambda v: np.array(float(v.detach()), dtype=np.float64))
+    out = {}
+    for shp, regime in LOSS_EDGE_RGB.items():
+        H, W = (int(v) for v in shp.split("x"))
+        gt = torch.rand(3, H, W, generator=g)
+        if regime == "near":
+            img = gt + 1e-3 * torch.randn(3, H, W, generator=g)
+        else:
+            img = torch.rand(3, H, W, generator=g)
+            if regime == "ties":
+                img[:, :, :W // 2] = gt[:, :, :W // 2]
+        gta = (torch.rand(1, H, W, generator=g) > 0.4).float()
+        alpha = torch.rand(1, H, W, generator=g)
+        if H * W > 1:
+            alpha[:, :(H + 1) // 2, :(W + 1) // 2] = gta[:, :(H + 1) // 2, :(W + 1) // 2]      # saturated alpha: exact ties
+        t = f"rgb{shp}"
+        out.update({f"{t}_img": f32(img), f"{t}_gt": f32(gt), f"{t}_alpha": f32(alpha), f"{t}_gta": f32(gta)})
+        out.update({f"{t}_Ll1": f64(l1_loss(img, gt)), f"{t}_ssim": f64(ssim_loss(img, gt))})
+        for name, lam in (("l0", 0.0), ("l1", 1.0), ("l02", 0.2)):
+            i = img.clone().requires_grad_(True)
+            ((1.0 - lam) * l1_loss(i, gt) + lam * (1.0 - ssim_loss(i, gt))).backward()
+            out[f"{t}_dimg_{name}"] = f32(i.grad)
+        a = alpha.clone().requires_grad_(True)
+        La = l1_loss(a, gta)
+        La.backward()
+        out.update({f"{t}_Lalpha": f64(La), f"{t}_dalpha": f32(a.grad)})
+    for shp in LOSS_EDGE_GEOM:
+        H, W = (int(v) for v in shp.split("x"))
+        yy, xx = torch.meshgrid(torch.arange(H), torch.arange(W), indexing="ij")
+        # piecewise-constant normals (3x3 blocks) with a zero region, as a render has on the background: ties in the smoothness term
+        norm = (torch.randn(3, H // 3 + 1, W // 3 + 1, generator=g) * 0.5).repeat_interleave(3, 1).repeat_interleave(3, 2)[:, :H, :W]
+        norm = norm * ((xx + yy) < 2 * (H + W) // 3).float()
+        gtn = torch.randn(3, H, W, generator=g)
+        gtn = gtn / gtn.norm(dim=0, keepdim=True)
+        gti = (torch.rand(3, H // 6 + 1, W // 6 + 1, generator=g).repeat_interleave(6, 1).repeat_interleave(6, 2)[:, :H, :W]
+               + 0.05 * torch.rand(3, H, W, generator=g)).clamp(0, 1)
+        mask = torch.rand(1, H, W, generator=g) * (torch.rand(1, H, W, generator=g) > 0.25).float()      # fractional, with zeros
+        gtd = 3.0 + torch.rand(1, H, W, generator=g)
+        depth = 3.0 + torch.rand(1, H, W, generator=g)
+        if H * W > 1:
+            depth[:, :(H + 1) // 2, :(W + 1) // 2] = gtd[:, :(H + 1) // 2, :(W + 1) // 2]
+        t = f"geo{shp}"
+        out.update({f"{t}_norm": f32(norm), f"{t}_gtn": f32(gtn), f"{t}_gti": f32(gti), f"{t}_mask": f32(mask),
+                    f"{t}_depth": f32(depth), f"{t}_gtd": f32(gtd)})
+        n = norm.clone().requires_grad_(True)
+        Ln = norm_loss(n, gtn, mask)
+        Ln.backward()
+        out.update({f"{t}_Lnorm": f64(Ln), f"{t}_dnorm_n": f32(n.grad)})
+        for name, gamma in (("g01", 0.1), ("g001", 0.01)):
+            n = norm.clone().requires_grad_(True)
+            Ls = smooth_loss(gti, n, mask, gamma)
+            Ls.backward()
+            out.update({f"{t}_Lnsm_{name}": f64(Ls), f"{t}_dnorm_s_{name}": f32(n.grad)})
+        d = depth.clone().requires_grad_(True)
+        Ld = l1_loss(d, gtd)
+        Ld.backward()
+        out.update({f"{t}_Ld": f64(Ld), f"{t}_ddepth": f32(d.grad)})
+    np.savez_compressed(os.path.join(HERE, "loss_edges.npz"), **out)
 
 
 def norm_from_depth():
@@ -393,7 +471,7 @@ def op_small():
 
 
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["cameras", "sh", "cube", "losses", "geom_losses", "norm_from_depth", "host_terms", "uvnet", "texture_io", "checkpoint", "op_small"]
+    which = sys.argv[1:] or ["cameras", "sh", "cube", "losses", "geom_losses", "loss_edges", "norm_from_depth", "host_terms", "uvnet", "texture_io", "checkpoint", "op_small"]
     for name in which:
         globals()[name]()
     print("golden fixtures written to", HERE)

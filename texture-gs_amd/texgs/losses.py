@@ -9,19 +9,39 @@ import torch
 from . import _lib
 
 
+def _check_count(name, t, channels, H, W):
+    """A kernel indexes every map as [channels, H, W] of the image it runs on: anything with another element count is read
+    out of bounds.  Same-count shapes ([H,W] for [1,H,W]) pass, as `.contiguous()` makes them the same memory."""
+    if t is None:
+        raise ValueError(f"{name} is None but a term with a non-zero lambda reads it")
+    if t.numel() != channels * H * W:
+        raise ValueError(f"{name} has shape {tuple(t.shape)}, expected {channels * H * W} elements for an image of "
+                         f"shape {(channels, H, W)}")
+
+
+def _check_device(dev, **tensors):
+    if dev.type != "cuda":
+        raise RuntimeError("texgs.losses runs on an AMD GPU; there is no CPU fallback")
+    for name, t in tensors.items():
+        if t is not None and t.device != dev:
+            raise ValueError(f"{name} is on {t.device}, expected {dev}")
+
+
 class _RgbAlphaLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, image, gt_image, alpha, gt_alpha, lambda_dssim, lambda_alpha):
-        lib = _lib.load()
-        dev = image.device
-        if dev.type != "cuda":
-            raise RuntimeError("texgs.losses runs on an AMD GPU; there is no CPU fallback")
+        if image.dim() != 3 or image.shape[0] != 3 or gt_image.shape != image.shape:
+            raise ValueError(f"image and gt_image must both be [3,H,W], got {tuple(image.shape)} and {tuple(gt_image.shape)}")
         _, H, W = image.shape
+        use_alpha = lambda_alpha != 0.0
+        if use_alpha:
+            _check_count("alpha", alpha, 1, H, W)
+            _check_count("gt_alpha", gt_alpha, 1, H, W)
+        dev = image.device
+        _check_device(dev, gt_image=gt_image, alpha=alpha if use_alpha else None, gt_alpha=gt_alpha if use_alpha else None)
+        lib = _lib.load()
         img = image.detach().to(torch.float32).contiguous()
         gt = gt_image.detach().to(torch.float32).contiguous()
-        if img.shape != gt.shape or img.shape[0] != 3:
-            raise ValueError("image and gt_image must both be [3,H,W]")
-        use_alpha = alpha is not None and gt_alpha is not None and lambda_alpha != 0.0
         a = alpha.detach().to(torch.float32).contiguous() if use_alpha else None
         ga = gt_alpha.detach().to(torch.float32).contiguous() if use_alpha else None
         scratch = torch.empty(9 * H * W, dtype=torch.float32, device=dev)
@@ -61,23 +81,46 @@ def rgb_alpha_loss(image, gt_image, alpha=None, gt_alpha=None, lambda_dssim=0.2,
 class _GeomLosses(torch.autograd.Function):
     @staticmethod
     def forward(ctx, norm, gt_norm, gt_image, mask, depth, gt_depth, lambda_norm, lambda_smooth, gamma, lambda_depth):
-        lib = _lib.load()
-        ref = norm if norm is not None else depth
-        dev = ref.device
-        if dev.type != "cuda":
-            raise RuntimeError("texgs.losses runs on an AMD GPU; there is no CPU fallback")
+        use_n = lambda_norm != 0.0 or lambda_smooth != 0.0
+        use_d = lambda_depth != 0.0
+        ref = norm if use_n else depth if use_d else (norm if norm is not None else depth)      # the map that sets H and W
+        # a tensor of a term whose lambda is 0 is neither checked nor handed to the kernels
+        if not use_n:
+            norm = mask = None
+        if lambda_norm == 0.0:
+            gt_norm = None
+        if lambda_smooth == 0.0:
+            gt_image = None
+        if not use_d:
+            depth = gt_depth = None
+        if ref is None or ref.dim() < 2:
+            raise ValueError("norm (for the normal and smoothness terms) or depth (for the depth term) must be a [C,H,W] map")
         H, W = ref.shape[-2:]
+        if use_n:
+            _check_count("norm", norm, 3, H, W)
+            if mask is not None:
+                _check_count("mask", mask, 1, H, W)
+        if lambda_norm != 0.0:
+            _check_count("gt_norm", gt_norm, 3, H, W)
+        if lambda_smooth != 0.0:
+            _check_count("gt_image", gt_image, 3, H, W)
+        if use_d:
+            _check_count("depth", depth, 1, H, W)
+            _check_count("gt_depth", gt_depth, 1, H, W)
+            if use_n and tuple(depth.shape[-2:]) != (H, W):
+                raise ValueError(f"depth has shape {tuple(depth.shape)}, norm has shape {tuple(norm.shape)}: they must share H and W")
+        dev = ref.device
+        _check_device(dev, norm=norm, gt_norm=gt_norm, gt_image=gt_image, mask=mask, depth=depth, gt_depth=gt_depth)
+        lib = _lib.load()
         c = lambda t: None if t is None else t.detach().to(torch.float32).contiguous()
         n, gn, gi, m, d, gd = c(norm), c(gt_norm), c(gt_image), c(mask), c(depth), c(gt_depth)
-        use_n = n is not None and (lambda_norm != 0.0 or lambda_smooth != 0.0)
-        use_d = d is not None and lambda_depth != 0.0
         sums = torch.empty(12, dtype=torch.float32, device=dev)
         d_n = torch.empty_like(n) if use_n else None
         d_d = torch.empty_like(d) if use_d else None
         p = lambda t: None if t is None else t.data_ptr()
         with torch.cuda.device(dev):
             _lib.check(lib.texgs_geom_losses(p(n), p(gn), p(gi), p(m), p(d), p(gd), H, W, float(lambda_norm), float(lambda_smooth),
-                                             float(gamma), float(lambda_depth) if use_d else 0.0, p(sums), p(d_n), p(d_d),
+                                             float(gamma), float(lambda_depth), p(sums), p(d_n), p(d_d),
                                              torch.cuda.current_stream(dev).cuda_stream), "texgs_geom_losses")
         loss = sums.new_zeros(())
         stats = {}
