@@ -502,6 +502,36 @@ typedef struct {
 } TexGSDensityMove;
 int texgs_density_move(const TexGSDensityMove* move, void* stream);
 
+/* ---- evaluation metrics (additive in v19; csrc/metrics.hip; train.py:45-93, utils/metrics.py) -----------------------------------------
+ * The version stays 19: nothing that existed changes; a loader looks the two symbols up (texgs/_lib.py EXPORTS).
+ * Every sum that L1, PSNR, SSIM and the normal MAE of one view need: one launch over the view and a one-block reduce in a fixed
+ * order, no atomics (a row is bit-identical from run to run), nothing read back.
+ *   image, gt_image  f32[3,H,W]; with clamp01 != 0 both are clamped to [0, 1] on load (train.py:52,58)
+ *   norm, gt_norm    f32[3,H,W], both NULL or both set; never clamped
+ *   alpha            f32[1,H,W] or NULL: the weight of the normal MAE; never clamped; ignored without normals
+ * d = image - gt_image is ONE fp32 subtraction; everything after it is fp64.  SSIM is
+ * skimage.metrics.structural_similarity(channel_axis=0, data_range=1.0) per channel: uniform 7x7 window, cov_norm = 49/48,
+ * C1 = 1e-4, C2 = 9e-4, summed over the map cropped by 3 pixels on every side.  The angle between normals is
+ * acos(clamp(x.y / (max(|x|, 1e-6) max(|y|, 1e-6)), -1, 1)) in degrees.
+ * row f64[TEXGS_METRICS_ROW] (device):
+ *   [0]     sum |d| over the three channels          [1..3]  sum d^2 per channel          [4..6]  sum S per channel (cropped map)
+ *   [7]     MAE numerator: sum deg * alpha (sum deg without alpha; 0 without normals)
+ *   [8]     MAE denominator: sum alpha (H W without alpha; 0 without normals)
+ *   [9]     H W          [10]  (H - 6)(W - 6)          [11..15]  0
+ * temp: texgs_eval_metrics_temp_bytes(H, W) bytes of device memory, 8-byte aligned.  H or W below 7 is an error (the window does not
+ * fit: skimage raises), as is a NULL image, gt_image, temp or row; all checked on the host before any launch. */
+#define TEXGS_METRICS_ROW     16
+#define TEXGS_METRICS_L1      0
+#define TEXGS_METRICS_SE      1
+#define TEXGS_METRICS_SSIM    4
+#define TEXGS_METRICS_MAE_NUM 7
+#define TEXGS_METRICS_MAE_DEN 8
+#define TEXGS_METRICS_PIXELS  9
+#define TEXGS_METRICS_CROPPED 10
+size_t texgs_eval_metrics_temp_bytes(int32_t H, int32_t W);
+int texgs_eval_metrics(const float* image, const float* gt_image, const float* norm, const float* gt_norm, const float* alpha,
+                       int32_t H, int32_t W, int32_t clamp01, void* temp, double* row, void* stream);
+
 /* Hardware self-test of the wave64 cross-lane primitives the backward's reductions use (csrc/wave_ops.h: DPP lane^4 /
  * lane^8 exchanges, permlane16/32 swaps, both transposing butterflies).  seed: f32[128] device; out: f32[576] device,
  * nine blocks of 64 differences against the __shfl_xor formulation -- all exactly 0 on gfx950. */

@@ -2,7 +2,8 @@
 
 Objects are rebuilt only when their sources are newer.  preprocess.hip is built with -ffp-contract=off (its
 fp32 operation order is part of the bit-exact key/rect/radius contract) and so is points.hip (its squared distance is
-compared bit for bit) and density.hip (its per-step statistics likewise); the render kernels allow contraction
+compared bit for bit), density.hip (its per-step statistics likewise) and metrics.hip (its fp64 sums are compared with numpy's);
+the render kernels allow contraction
 and use hardware fp32 atomics (-munsafe-fp-atomics).
 """
 import os
@@ -32,6 +33,7 @@ UNITS = {
     "points.hip": ["-ffp-contract=off"],      # its squared distance is a bit-exact contract: no fused multiply-add
     "cubetex.hip": ["-munsafe-fp-atomics"],   # the texture gradient's scatter: hardware fp32 atomic adds
     "density.hip": ["-ffp-contract=off"],     # the per-step statistics are a bit-exact contract: x*x + y*y with separate roundings
+    "metrics.hip": ["-ffp-contract=off"],     # fp64 sums of exact fp32 products, reproducible against numpy: no fused multiply-add
     "abi.hip": [],
 }
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "wave_ops.h"), os.path.join(CSRC, "render_bwd_body.h"),

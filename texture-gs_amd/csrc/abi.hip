@@ -542,6 +542,19 @@ int texgs_density_move(const TexGSDensityMove* m, void* stream) {
     return 0;
 }
 
+size_t texgs_eval_metrics_temp_bytes(int32_t H, int32_t W) { return eval_metrics_temp_bytes(H, W); }
+
+int texgs_eval_metrics(const float* image, const float* gt_image, const float* norm, const float* gt_norm, const float* alpha,
+                       int32_t H, int32_t W, int32_t clamp01, void* temp, double* row, void* stream) {
+    if (!image || !gt_image || !temp || !row) return fail_msg("NULL argument");
+    if (H < 7 || W < 7) return fail_msg("H and W must be at least 7: the 7x7 SSIM window does not fit");
+    if ((!norm) != (!gt_norm)) return fail_msg("norm and gt_norm must be both NULL or both set");
+    if ((((int64_t)W + 31) / 32) * (((int64_t)H + 31) / 32) >= (1ll << 31)) return fail_msg("image too large: 2^31 tiles or more");
+    if (int r = launch_eval_metrics(image, gt_image, norm, gt_norm, alpha, H, W, clamp01 != 0, temp, row, (hipStream_t)stream))
+        return fail("eval_metrics", (hipError_t)r);
+    return 0;
+}
+
 int texgs_selftest_waveops(const float* seed128, float* out576, void* stream) {
     if (!seed128 || !out576) return fail_msg("NULL argument");
     launch_selftest_waveops(seed128, out576, (hipStream_t)stream);

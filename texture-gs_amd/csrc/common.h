@@ -111,3 +111,6 @@ int launch_density_stats(const float* grad, const int32_t* radii, int n, float* 
 size_t density_plan_temp_bytes(int n);
 int launch_density_plan(const TexGSDensityPlan* p, uint8_t* action, int32_t* rank, uint32_t* totals, void* temp, hipStream_t s);
 int launch_density_move(const TexGSDensityMove* m, hipStream_t s);
+size_t eval_metrics_temp_bytes(int H, int W);
+int launch_eval_metrics(const float* image, const float* gt_image, const float* norm, const float* gt_norm, const float* alpha, int H,
+                        int W, int clamp01, void* temp, double* row, hipStream_t s);

@@ -76,6 +76,7 @@ class UVNetGradStruct(C.Structure):
 DENSITY_KEEP, DENSITY_CLONE, DENSITY_CLONE_KEPT, DENSITY_SPLIT, DENSITY_CHILD = 1, 2, 4, 8, 16      # TEXGS_DENSITY_* action bits
 DENSITY_ROW = {"copy": 0, "moment": 1, "scaling": 2, "xyz": 3}                                      # TEXGS_DENSITY_ROW_*
 DENSITY_MAX_ROWS = 24
+METRICS_ROW = 16         # f64 slots of one view's row (TEXGS_METRICS_*): 0 sum|d|, 1-3 sum d^2, 4-6 sum S, 7/8 MAE num/den, 9 HW, 10 cropped
 
 
 class DensityPlanStruct(C.Structure):
@@ -107,7 +108,8 @@ EXPORTS = ["texgs_abi_version", "texgs_build_id", "texgs_last_error", "texgs_sca
            "texgs_chamfer_nn_temp_bytes", "texgs_chamfer_nn",
            "texgs_knn3_temp_bytes", "texgs_knn3_mean_dist2", "texgs_fps_temp_bytes", "texgs_farthest_points",
            "texgs_cube_sample", "texgs_cube_latlong", "texgs_cube_sample_backward", "texgs_cube_sample_nearest_backward",
-           "texgs_density_stats", "texgs_density_plan_temp_bytes", "texgs_density_plan", "texgs_density_move"]
+           "texgs_density_stats", "texgs_density_plan_temp_bytes", "texgs_density_plan", "texgs_density_move",
+           "texgs_eval_metrics_temp_bytes", "texgs_eval_metrics"]
 KERNEL_NAMES = ["preprocess_fwd", "scan", "duplicate", "sort", "ranges", "render_fwd", "render_bwd", "preprocess_bwd",
                 "texgrad_reduce"]
 
@@ -209,6 +211,10 @@ def load():
     lib.texgs_density_plan.restype = C.c_int
     lib.texgs_density_move.argtypes = [P(DensityMoveStruct), C.c_void_p]
     lib.texgs_density_move.restype = C.c_int
+    lib.texgs_eval_metrics_temp_bytes.argtypes = [C.c_int32, C.c_int32]
+    lib.texgs_eval_metrics_temp_bytes.restype = C.c_size_t
+    lib.texgs_eval_metrics.argtypes = [C.c_void_p] * 5 + [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.texgs_eval_metrics.restype = C.c_int
     lib.texgs_selftest_waveops.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     lib.texgs_selftest_waveops.restype = C.c_int
     lib.texgs_profile_enable.argtypes = [C.c_int]

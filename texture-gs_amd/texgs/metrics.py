@@ -1,0 +1,188 @@
+"""Evaluation metrics (train.py:45-93 `visualize`, utils/metrics.py) on the device: L1, PSNR, SSIM and the normal MAE of a view from
+ONE launch of csrc/metrics.hip, which leaves every sum the four need in a row of 16 float64 values (include/texgs.h
+TEXGS_METRICS_*).  The reference copies both images to the host for skimage's SSIM and reads three scalars back per view; here
+`Evaluator.add` enqueues and returns, and `Evaluator.result` reads the whole table back once.
+
+`mse`, `psnr`, `ssim`, `mae` and `avg_error` keep the reference's signatures and return types.  SSIM is
+skimage.metrics.structural_similarity(channel_axis=0, data_range=1.0) -- uniform 7x7 window, sample covariance, border of 3 cropped
+-- NOT the training loss of texgs.losses (11x11 Gaussian window, zero padding, population covariance).  Images are float32 [3,H,W]
+with H, W >= 7 (the window has to fit; skimage raises too), contiguous, on the GPU: there is no CPU fallback.
+
+Not here: LPIPS (its network weights are not part of this project) and the JET depth colour map of train.py:22-37."""
+import numpy as np
+import torch
+
+from . import _lib
+from .losses import _check_count, _check_device
+
+ROW = _lib.METRICS_ROW
+
+
+def _check_map(name, t, channels, H, W):
+    _check_count(name, t, channels, H, W)
+    if t.dtype != torch.float32:
+        raise ValueError(f"{name} must be torch.float32, got {t.dtype}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name} must be contiguous")
+
+
+def _check_view(image, gt_image, norm, gt_norm, alpha):
+    """Everything a launch relies on, before any library call -> (H, W, alpha as float32 or None)"""
+    if not torch.is_tensor(image) or not torch.is_tensor(gt_image) or image.dim() != 3 or image.shape[0] != 3 \
+            or gt_image.shape != image.shape:
+        raise ValueError("image and gt_image must both be [3,H,W], got "
+                         f"{tuple(getattr(image, 'shape', ()))} and {tuple(getattr(gt_image, 'shape', ()))}")
+    _, H, W = image.shape
+    if H < 7 or W < 7:
+        raise ValueError(f"H and W must be at least 7 (the 7x7 SSIM window has to fit), got {H}x{W}")
+    _check_map("image", image, 3, H, W)
+    _check_map("gt_image", gt_image, 3, H, W)
+    if (norm is None) != (gt_norm is None):
+        raise ValueError("norm and gt_norm must be given together")
+    if norm is not None:
+        for name, t in (("norm", norm), ("gt_norm", gt_norm)):
+            if not torch.is_tensor(t) or t.dim() != 3 or tuple(t.shape) != (3, H, W):
+                raise ValueError(f"{name} must be [3,{H},{W}], got {tuple(getattr(t, 'shape', ()))}")
+            _check_map(name, t, 3, H, W)
+    if alpha is not None:
+        if norm is None:
+            raise ValueError("alpha weights the normal MAE: it needs norm and gt_norm")
+        if not torch.is_tensor(alpha):
+            raise ValueError("alpha must be a tensor of H W elements")
+        _check_count("alpha", alpha, 1, H, W)
+        if not alpha.is_contiguous():
+            raise ValueError("alpha must be contiguous")
+    if image.device.type != "cuda":
+        raise RuntimeError("texgs.metrics runs on an AMD GPU; there is no CPU fallback")
+    _check_device(image.device, gt_image=gt_image, norm=norm, gt_norm=gt_norm, alpha=alpha)
+    if alpha is not None:
+        alpha = alpha.float()           # (the reference's `alpha.float()`: a bool mask is converted on the device)
+    return H, W, alpha
+
+
+def _launch(image, gt_image, norm, gt_norm, alpha, H, W, clamp, table, v):
+    """Enqueue the view's kernels on the current stream; they write row v of `table` (f64 [capacity, 16])"""
+    lib = _lib.load()
+    dev = image.device
+    temp = torch.empty(lib.texgs_eval_metrics_temp_bytes(H, W) // 8, dtype=torch.float64, device=dev)
+    p = lambda t: None if t is None else t.data_ptr()
+    with torch.cuda.device(dev):
+        _lib.check(lib.texgs_eval_metrics(p(image), p(gt_image), p(norm), p(gt_norm), p(alpha), H, W, 1 if clamp else 0, p(temp),
+                                          table.data_ptr() + v * ROW * 8, torch.cuda.current_stream(dev).cuda_stream),
+                   "texgs_eval_metrics")
+
+
+def _det(*ts):
+    return tuple(t.detach() if torch.is_tensor(t) else t for t in ts)     # (anything else is refused by _check_view)
+
+
+def _row(image, gt_image, norm=None, gt_norm=None, alpha=None, clamp=False):
+    """One view's row as a device tensor f64[16]"""
+    image, gt_image, norm, gt_norm, alpha = _det(image, gt_image, norm, gt_norm, alpha)
+    H, W, alpha = _check_view(image, gt_image, norm, gt_norm, alpha)
+    table = torch.empty(1, ROW, dtype=torch.float64, device=image.device)
+    _launch(image, gt_image, norm, gt_norm, alpha, H, W, clamp, table, 0)
+    return table[0]
+
+
+def mse(img1, img2):
+    """utils/metrics.py:18-19: per-channel mean squared error, a [3,1] float32 tensor on the device (nothing is read back)"""
+    r = _row(img1, img2)
+    return (r[1:4] / r[9]).to(torch.float32).view(3, 1)
+
+
+def psnr(img1, img2):
+    """utils/metrics.py:21-23: 20 log10(1 / sqrt(mse)) per channel, [3,1] float32 on the device; an identical pair gives inf"""
+    r = _row(img1, img2)
+    return (20.0 * torch.log10(1.0 / torch.sqrt(r[1:4] / r[9]))).to(torch.float32).view(3, 1)
+
+
+def ssim(img1, img2):
+    """utils/metrics.py:40-46: the mean over channels of skimage's mean SSIM, a Python float.  One readback of three sums; the
+    images stay on the device."""
+    r = _row(img1, img2)[4:11].cpu().numpy()
+    return float(np.mean(r[0:3] / r[6]))
+
+
+def mae(norm1, norm2, alpha=None):
+    """utils/metrics.py:25-37: mean angle between two normal maps in degrees, weighted by alpha when given; a 0-d float32 tensor on
+    the device.  NaN when alpha sums to zero, as in the reference.  (The kernel works on a view: the normals stand in for its image
+    pair, whose sums are not used.)"""
+    r = _row(norm1, norm2, norm1, norm2, alpha)
+    return (r[7] / r[8]).to(torch.float32)
+
+
+def avg_error(psnr, ssim, lpips):
+    """The 'average' error used in the paper (utils/metrics.py:60-67), host arithmetic."""
+    def psnr_to_mse(psnr):
+        return np.exp(-0.1 * np.log(10.) * psnr)
+    mse = psnr_to_mse(psnr)
+    dssim = np.sqrt(1 - ssim)
+    return np.exp(np.mean(np.log(np.array([mse, dssim, lpips])))).item()
+
+
+def finish_rows(rows, has_norm):
+    """The host half of `Evaluator.result`: rows float64 [V, 16] as the kernel wrote them, has_norm one bool per view ->
+    dict(views, l1, psnr, ssim, mae), float64 arithmetic.  l1, psnr and ssim are means over views of the per-view values as
+    train.py:67-69,90-92 average them (PSNR per channel, then over channels, then over views); mae is the mean over the views that
+    had normals of their (alpha-weighted) mean angle in degrees, None when no view had any."""
+    rows = np.asarray(rows, dtype=np.float64).reshape(-1, ROW)
+    V = rows.shape[0]
+    has_norm = np.asarray(has_norm, dtype=bool).reshape(-1)
+    if has_norm.shape[0] != V:
+        raise ValueError(f"has_norm holds {has_norm.shape[0]} entries for {V} rows")
+    if V == 0:
+        return dict(views=0, l1=None, psnr=None, ssim=None, mae=None)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        l1 = rows[:, 0] / (3.0 * rows[:, 9])
+        ps = (20.0 * np.log10(1.0 / np.sqrt(rows[:, 1:4] / rows[:, 9:10]))).mean(axis=1)
+        ss = (rows[:, 4:7] / rows[:, 10:11]).mean(axis=1)
+        ma = rows[has_norm, 7] / rows[has_norm, 8]
+    return dict(views=V, l1=float(l1.mean()), psnr=float(ps.mean()), ssim=float(ss.mean()),
+                mae=float(ma.mean()) if ma.size else None)
+
+
+class Evaluator:
+    """The evaluation loop of train.py:45-93 without its per-view readbacks:
+
+        ev = Evaluator(capacity=len(cameras))
+        for view in cameras:
+            ev.add(image, gt_image, norm=norm, gt_norm=gt_normal, alpha=gt_alpha)     # enqueues; synchronises nothing
+        res = ev.result()                                                             # one readback
+
+    `clamp=True` clamps image and gt_image to [0, 1] in the kernel (train.py:52,58); normals and alpha are never clamped."""
+
+    def __init__(self, capacity):
+        capacity = int(capacity)
+        if capacity < 1:
+            raise ValueError("capacity must be at least 1")
+        self.capacity = capacity
+        self._table = None          # f64 [capacity, 16] on the device of the first view
+        self._has_norm = []
+
+    def __len__(self):
+        return len(self._has_norm)
+
+    def add(self, image, gt_image, norm=None, gt_norm=None, alpha=None, clamp=True):
+        image, gt_image, norm, gt_norm, alpha = _det(image, gt_image, norm, gt_norm, alpha)
+        H, W, alpha = _check_view(image, gt_image, norm, gt_norm, alpha)
+        v = len(self._has_norm)
+        if v >= self.capacity:
+            raise RuntimeError(f"the evaluator holds {self.capacity} views already (its capacity)")
+        if self._table is None:
+            self._table = torch.zeros(self.capacity, ROW, dtype=torch.float64, device=image.device)
+        elif self._table.device != image.device:
+            raise ValueError(f"image is on {image.device}, the earlier views were on {self._table.device}")
+        _launch(image, gt_image, norm, gt_norm, alpha, H, W, clamp, self._table, v)
+        self._has_norm.append(norm is not None)
+
+    def rows(self):
+        """The raw table of the views added so far, float64 [views, 16] on the device"""
+        v = len(self._has_norm)
+        if self._table is None:
+            return torch.zeros(0, ROW, dtype=torch.float64)
+        return self._table[:v]
+
+    def result(self):
+        rows = self.rows()
+        return finish_rows(rows.cpu().numpy(), self._has_norm)
