@@ -1,6 +1,6 @@
 """-m "not gpu": the C-ABI library builds (hipcc cross-compiles without a GPU), loads, exports every symbol that
-include/texgs.h declares, and the ctypes mirrors in texgs/_lib.py have the C structs' sizes and field offsets.
-No compute calls here."""
+include/texgs.h declares, the ctypes mirrors in texgs/_lib.py have the C structs' sizes and field offsets, and its signature
+table agrees with the header's prototypes.  No compute calls here."""
 import ctypes
 import os
 import re
@@ -36,17 +36,33 @@ def test_library_exports_every_declared_symbol(lib_built):
     assert _lib.load().texgs_abi_version() == _lib.ABI_VERSION
 
 
+def mirrors():
+    """{C struct name: ctypes mirror} for EVERY ctypes.Structure that texgs/_lib.py defines: `Frame` mirrors `TexGSFrame`,
+    `UVNetStruct` mirrors `TexGSUVNet`.  A mirror added later is picked up here without being listed."""
+    from texgs import _lib
+    out = {}
+    for name, cls in vars(_lib).items():
+        if isinstance(cls, type) and issubclass(cls, ctypes.Structure) and cls is not ctypes.Structure:
+            out["TexGS" + (name[:-len("Struct")] if name.endswith("Struct") else name)] = cls
+    return out
+
+
 def test_ctypes_structs_match_c_layout(tmp_path):
     from texgs import _lib
-    structs = {"TexGSFrame": _lib.Frame, "TexGSInputs": _lib.Inputs, "TexGSGeom": _lib.Geom,
-               "TexGSBinning": _lib.Binning, "TexGSImage": _lib.Image, "TexGSGrads": _lib.Grads,
-               "TexGSUVNet": _lib.UVNetStruct, "TexGSUVNetGrad": _lib.UVNetGradStruct}
+    structs = mirrors()
+    assert len(structs) == 12 and {"TexGSFrame", "TexGSHashGrid", "TexGSDensityPlan", "TexGSDensityRow", "TexGSDensityMove"} <= set(structs)
+    consts = {"TEXGS_ABI_VERSION": _lib.ABI_VERSION, "TEXGS_TILE": _lib.TILE, "TEXGS_REC_TEST_FLOATS": _lib.REC_TEST_FLOATS,
+              "TEXGS_REC_SHADE_FLOATS": _lib.REC_SHADE_FLOATS, "TEXGS_ACC_FLOATS": _lib.ACC_FLOATS,
+              "TEXGS_TEXBIN_RECORD_FLOATS": _lib.TEXBIN_RECORD_FLOATS, "TEXGS_RESV_WORDS": _lib.RESV_WORDS,
+              "TEXGS_DENSITY_MAX_ROWS": _lib.DENSITY_MAX_ROWS, "TEXGS_METRICS_ROW": _lib.METRICS_ROW,
+              "TEXGS_HASHGRID_MAX_LEVELS": _lib.HASHGRID_MAX_LEVELS, "TEXGS_HASHGRID_FEATURES": _lib.HASHGRID_FEATURES}
     lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "texgs.h"', 'int main(void) {']
     for cname, cls in structs.items():
         lines.append(f'printf("{cname} %zu\\n", sizeof({cname}));')
         for fname, _ in cls._fields_:
             lines.append(f'printf("{cname}.{fname} %zu\\n", offsetof({cname}, {fname}));')
-    lines.append('printf("consts %d %d %d %d %d %d\\n", TEXGS_ABI_VERSION, TEXGS_TILE, TEXGS_REC_TEST_FLOATS, TEXGS_REC_SHADE_FLOATS, TEXGS_ACC_FLOATS, TEXGS_TEXBIN_RECORD_FLOATS);')
+    for cname in consts:
+        lines.append(f'printf("{cname} %d\\n", (int)({cname}));')
     lines.append('return 0; }')
     src = tmp_path / "layout.c"
     src.write_text("\n".join(lines))
@@ -58,8 +74,97 @@ def test_ctypes_structs_match_c_layout(tmp_path):
         assert int(got[cname][0]) == ctypes.sizeof(cls), cname
         for fname, _ in cls._fields_:
             assert int(got[f"{cname}.{fname}"][0]) == getattr(cls, fname).offset, (cname, fname)
-    assert [int(x) for x in got["consts"]] == [_lib.ABI_VERSION, _lib.TILE, _lib.REC_TEST_FLOATS, _lib.REC_SHADE_FLOATS,
-                                               _lib.ACC_FLOATS, _lib.TEXBIN_RECORD_FLOATS]
+    for cname, value in consts.items():
+        assert int(got[cname][0]) == value, cname
+
+
+def header_prototypes():
+    """{name: (return type, [argument types])} of every function that include/texgs.h declares, as C type strings without the
+    argument names and without `const` (`const TexGSFrame* frame` -> `TexGSFrame*`)."""
+    src = open(HDR).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    src = re.sub(r"//[^\n]*", "", src)
+    ctype = lambda decl: re.sub(r"\s+", "", re.sub(r"\bconst\b", "", decl))
+    protos = {}
+    for ret, name, args in re.findall(r"^\s*((?:const\s+)?\w+\s*\*?)\s*(texgs_\w+)\s*\(([^)]*)\)\s*;", src, flags=re.M):
+        args = [a.strip() for a in args.split(",")]
+        args = [] if args == ["void"] else [ctype(re.sub(r"\w+$", "", a)) for a in args]       # drop the argument's name
+        protos[name] = (ctype(ret), args)
+    return protos
+
+
+C_SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "uint32_t": ctypes.c_uint32, "size_t": ctypes.c_size_t,
+             "float": ctypes.c_float}
+
+
+def same_scalar(a, b):
+    """Two ctypes scalar types of the same width and kind (signed / unsigned integer, float)"""
+    kind = lambda t: "int" if t._type_ in "bhilq" else "uint" if t._type_ in "BHILQ" else t._type_
+    simple = lambda t: isinstance(t, type) and issubclass(t, ctypes._SimpleCData) and t._type_ in "bhilqBHILQfd"
+    return simple(a) and simple(b) and ctypes.sizeof(a) == ctypes.sizeof(b) and kind(a) == kind(b)
+
+
+def signature_mismatches(signatures):
+    """Every disagreement between a {name: (restype, argtypes)} table and the header's prototypes, as strings"""
+    protos, structs, bad = header_prototypes(), mirrors(), []
+    if sorted(signatures) != sorted(protos):
+        bad.append(f"names differ: {sorted(set(signatures) ^ set(protos))}")
+    for name, (restype, argtypes) in signatures.items():
+        if name not in protos:
+            continue
+        ret, args = protos[name]
+        if not (restype is ctypes.c_char_p if ret == "char*" else same_scalar(restype, C_SCALARS[ret])):
+            bad.append(f"{name}: returns {ret}, the table says {restype}")
+        if len(argtypes) != len(args):
+            bad.append(f"{name}: {len(args)} arguments, the table has {len(argtypes)}")
+            continue
+        for k, (c, t) in enumerate(zip(args, argtypes)):
+            is_pointer = t is ctypes.c_void_p or (isinstance(t, type) and issubclass(t, ctypes._Pointer))
+            if c in C_SCALARS:
+                ok = same_scalar(t, C_SCALARS[c])
+            elif c.endswith("*") and c[:-1] in structs:
+                ok = t is ctypes.c_void_p or t is ctypes.POINTER(structs[c[:-1]])
+            else:
+                ok = c.endswith("*") and not c.startswith("TexGS") and is_pointer
+            if not ok:
+                bad.append(f"{name}: argument {k} is {c}, the table says {t}")
+    return bad
+
+
+def test_signature_table_matches_the_header():
+    """texgs/_lib.py states each entry point's ctypes signature once (SIGNATURES); every one is compared with its prototype in
+    include/texgs.h: the return type, the argument count, and per argument a scalar of the same width and kind, the mirror of the
+    TexGS* struct pointed to (or void*), or a pointer for any other pointer.  ctypes converts silently, so a wrong width or a missing
+    argument would otherwise corrupt a call instead of failing it."""
+    from texgs import _lib
+    assert len(header_prototypes()) == 49
+    assert signature_mismatches(_lib.SIGNATURES) == []
+    # the check sees what it is for: one argument dropped, one int32_t widened to size_t, one struct mirror swapped
+    broken = dict(_lib.SIGNATURES)
+    ret, args = broken["texgs_cube_latlong"]
+    broken["texgs_cube_latlong"] = (ret, args[:-1])
+    assert any("texgs_cube_latlong: 8 arguments" in m for m in signature_mismatches(broken))
+    broken = dict(_lib.SIGNATURES, texgs_scan_temp_bytes=(ctypes.c_size_t, [ctypes.c_size_t]))
+    assert any("texgs_scan_temp_bytes: argument 0 is int32_t" in m for m in signature_mismatches(broken))
+    broken = dict(_lib.SIGNATURES, texgs_density_move=(ctypes.c_int, [ctypes.POINTER(_lib.DensityPlanStruct), ctypes.c_void_p]))
+    assert any("texgs_density_move: argument 0 is TexGSDensityMove*" in m for m in signature_mismatches(broken))
+
+
+def test_call_raises_with_the_entry_points_name(lib_built):
+    """_lib.call(fn, *args): a non-zero return code becomes a RuntimeError that names the function (from the ctypes function object)
+    and carries texgs_last_error(); a zero code returns quietly.  Host-only entry point: no GPU."""
+    import numpy as np
+    from texgs import _lib
+    lib = _lib.load()
+    with pytest.raises(RuntimeError, match=r"texgs_num_rendered_reduce failed \(code -1\): NULL argument"):
+        _lib.call(lib.texgs_num_rendered_reduce, None, 4, None, None)
+    buf = np.arange(3, dtype=np.uint32)
+    d, fp = ctypes.c_uint32(0), ctypes.c_uint64(0)
+    assert _lib.call(lib.texgs_num_rendered_reduce, buf.ctypes.data, 4, ctypes.byref(d), ctypes.byref(fp)) is None
+    assert d.value == 0 and fp.value == (2 << 32) | 1
+    import torch
+    t = torch.zeros(2)
+    assert _lib.ptr(None) is None and _lib.ptr(t) == t.data_ptr()
 
 
 def test_header_is_plain_c(tmp_path):

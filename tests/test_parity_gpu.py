@@ -79,6 +79,26 @@ def test_backward_matches_oracle_autograd(lib_built, case):
         assert ok, (name, msg)
 
 
+def test_debug_settings_change_no_result(lib_built):
+    """GaussianRasterizationSettings.debug = True makes every entry point of the operator synchronise its stream behind its launches
+    (TexGSFrame.debug, csrc/abi.hip) and changes nothing else: the forward outputs are bit-identical to the debug = False run, the
+    gradients (summed with float atomics, so not bit-reproducible between two runs) agree within helpers.grad_close.  The size of
+    __graft_entry__.smoke(): 400 Gaussians, 96 x 64, R = 32, one view."""
+    scene = synth.make_scene(400, 32, seed=21, scale_mean=0.05)
+    cam = synth.fibonacci_cameras(4, 96, 64)[1]
+    bg = torch.tensor([0.1, 0.0, 0.2])
+    target, nhat = synth.make_targets(cam.image_height, cam.image_width, seed=3)
+    run = lambda debug: Hh.hip_run(scene, cam, 2, bg, with_grad=True, target=target, nhat=nhat, depth_weight=0.05, debug=debug)
+    out, grads = run(False)
+    out_dbg, grads_dbg = run(True)
+    for k, name in enumerate(["image", "depth", "norm", "alpha", "radii"]):
+        assert torch.equal(out_dbg[k], out[k]), name
+    assert set(grads_dbg) == set(grads)
+    for name, exp in grads.items():
+        ok, msg = Hh.grad_close(grads_dbg[name], exp)
+        assert ok, (name, msg)
+
+
 def _tile_lists(point_list, ranges, drop):
     """{tile: [Gaussian ids in list order]} without the ids in `drop`."""
     pl = point_list.tolist()

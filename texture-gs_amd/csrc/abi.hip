@@ -2,7 +2,6 @@
 // boundary: int return codes + a thread-local error string.
 #include "common.h"
 #include <stdio.h>
-#include <string.h>
 #include <stdlib.h>
 
 #include <mutex>
@@ -21,21 +20,24 @@ uint32_t g_prof_mask = 0xFFFFFFFFu;       // kernel ids to bracket (an event pai
 std::vector<EvRec> g_prof_log;
 std::vector<hipEvent_t> g_prof_free;
 
-hipEvent_t prof_event() {
+hipEvent_t prof_event() {   // nullptr when the runtime cannot create one: that bracket is then dropped
     if (!g_prof_free.empty()) { hipEvent_t e = g_prof_free.back(); g_prof_free.pop_back(); return e; }
-    hipEvent_t e; (void)hipEventCreate(&e); return e;
+    hipEvent_t e = nullptr;
+    return hipEventCreate(&e) == hipSuccess ? e : nullptr;
 }
 
 struct ProfScope {          // brackets the launches issued inside its lifetime
     int kid; hipStream_t s; hipEvent_t a; bool on;
     ProfScope(int k, hipStream_t st) : kid(k), s(st), a(nullptr), on(false) {
         std::lock_guard<std::mutex> l(g_prof_mu);
-        if (g_prof_on && ((g_prof_mask >> k) & 1u)) { on = true; a = prof_event(); (void)hipEventRecord(a, s); }
+        if (g_prof_on && ((g_prof_mask >> k) & 1u)) { a = prof_event(); on = a != nullptr; if (on) (void)hipEventRecord(a, s); }
     }
     ~ProfScope() {
         if (!on) return;
         std::lock_guard<std::mutex> l(g_prof_mu);
-        hipEvent_t b = prof_event(); (void)hipEventRecord(b, s);
+        hipEvent_t b = prof_event();
+        if (!b) { g_prof_free.push_back(a); return; }
+        (void)hipEventRecord(b, s);
         g_prof_log.push_back({kid, a, b});
     }
 };
@@ -50,16 +52,12 @@ int fail_msg(const char* msg) {
     return -1;
 }
 
-// After every launch: cheap async check; with debug=1 also a stream sync (lineage `debug` semantics,
-// render/uv_tex_render.py:37).
-int check(const TexGSFrame* f, hipStream_t s, const char* where) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(where, e);
-    if (f->debug) {
-        e = hipStreamSynchronize(s);
-        if (e != hipSuccess) return fail(where, e);
-    }
-    return 0;
+// The one place where a launcher's status (common.h) becomes a return code: a HIP error is returned as itself, with
+// "<where>: <its string>" as the error text; with debug a stream sync follows (lineage `debug` semantics,
+// render/uv_tex_render.py:37) and its failure is reported the same way.
+int launched(const char* where, hipError_t st, hipStream_t s, bool debug) {
+    if (st == hipSuccess && debug) st = hipStreamSynchronize(s);
+    return st == hipSuccess ? 0 : fail(where, st);
 }
 
 int validate_frame(const TexGSFrame* f) {
@@ -108,17 +106,17 @@ int texgs_preprocess_forward(const TexGSFrame* frame, const TexGSInputs* in, Tex
     if (geom->scan_temp_bytes < scan_temp_bytes(frame->num_gaussians)) return fail_msg("scan_temp too small");
     hipStream_t s = (hipStream_t)stream;
     const CamConst c = make_cam(frame);
-    { ProfScope p(TEXGS_K_PREPROCESS_FWD, s); launch_preprocess_fwd(c, frame, in, geom, s); }
-    if (int r = check(frame, s, "preprocess_fwd")) return r;
-    return 0;
+    hipError_t st;
+    { ProfScope p(TEXGS_K_PREPROCESS_FWD, s); st = launch_preprocess_fwd(c, frame, in, geom, s); }
+    return launched("preprocess_fwd", st, s, frame->debug);
 }
 
 // K2: depth sort of the Gaussians + exclusive scan of tiles_touched in depth-rank order (independent of D)
-static int depth_sort_scan(const TexGSFrame* frame, TexGSGeom* geom, hipStream_t s) {
-    if (frame->num_gaussians == 0) return 0;
-    { ProfScope p(TEXGS_K_SCAN, s);
-      if (int r = launch_depth_sort_scan(geom, frame->num_gaussians, s)) return fail("depth sort / scan", (hipError_t)r); }
-    return check(frame, s, "depth sort / scan");
+static int depth_sort_scan(const TexGSGeom* geom, int32_t num_gaussians, hipStream_t s, bool debug) {
+    if (num_gaussians == 0) return 0;
+    hipError_t st;
+    { ProfScope p(TEXGS_K_SCAN, s); st = launch_depth_sort_scan(geom, num_gaussians, s); }
+    return launched("depth sort / scan", st, s, debug);
 }
 
 // D = sum of tiles_touched and the geometry fingerprint, read back in two steps so that a caller can issue K1 of a LATER view early
@@ -138,11 +136,7 @@ int texgs_num_rendered_begin(const TexGSGeom* geom, int32_t num_gaussians, uint3
     hipStream_t s = (hipStream_t)stream;
     hipError_t e = hipMemcpyAsync(host_pinned, bin_block_sums_ptr(geom, num_gaussians), nw * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
     if (e != hipSuccess) return fail("num_rendered readback", e);
-    if (sort_first) {
-        TexGSFrame f0; memset(&f0, 0, sizeof(f0)); f0.num_gaussians = num_gaussians;
-        if (int r = depth_sort_scan(&f0, const_cast<TexGSGeom*>(geom), s)) return r;
-    }
-    return 0;
+    return sort_first ? depth_sort_scan(geom, num_gaussians, s, false) : 0;
 }
 int texgs_num_rendered_reduce(const uint32_t* host_pinned, int32_t num_gaussians, uint32_t* host_out, uint64_t* fingerprint_out) {
     if (!host_pinned || !host_out) return fail_msg("NULL argument");
@@ -161,8 +155,7 @@ int texgs_num_rendered_reduce(const uint32_t* host_pinned, int32_t num_gaussians
 
 int texgs_depth_sort_scan(TexGSGeom* geom, int32_t num_gaussians, void* stream) {
     if (!geom) return fail_msg("NULL argument");
-    TexGSFrame f0; memset(&f0, 0, sizeof(f0)); f0.num_gaussians = num_gaussians;
-    return depth_sort_scan(&f0, geom, (hipStream_t)stream);
+    return depth_sort_scan(geom, num_gaussians, (hipStream_t)stream, false);
 }
 
 static int render_forward_impl(const TexGSFrame* frame, const TexGSInputs* in, const TexGSGeom* geom,
@@ -175,8 +168,9 @@ static int render_forward_impl(const TexGSFrame* frame, const TexGSInputs* in, c
         hipError_t e = hipMemsetAsync(img->tex_bin_count, 0, sizeof(uint32_t) * 2 * tex_bin_count(c.R), s);
         if (e != hipSuccess) return fail("tex_bin_count memset", e);
     }
-    { ProfScope p(TEXGS_K_RENDER_FWD, s); launch_render_fwd(c, frame, in, geom, bin, img, s); }
-    return check(frame, s, "render_fwd");
+    hipError_t st;
+    { ProfScope p(TEXGS_K_RENDER_FWD, s); st = launch_render_fwd(c, frame, in, geom, bin, img, s); }
+    return launched("render_fwd", st, s, frame->debug);
 }
 
 int texgs_render_forward(const TexGSFrame* frame, const TexGSInputs* in, const TexGSGeom* geom,
@@ -190,18 +184,18 @@ int texgs_bin_sort_render_forward(const TexGSFrame* frame, const TexGSInputs* in
     if (!in || !geom || !bin || !img) return fail_msg("NULL argument");
     hipStream_t s = (hipStream_t)stream;
     const CamConst c = make_cam(frame);
+    hipError_t st;
     if (bin->num_rendered > 0) {
         if (bin->sort_temp_bytes < sort_temp_bytes(bin->num_rendered, (uint32_t)(c.tiles_x * c.tiles_y))) return fail_msg("sort_temp too small");
-        { ProfScope p(TEXGS_K_DUPLICATE, s); launch_duplicate(c, geom, bin, s); }
-        if (int r = check(frame, s, "duplicate_with_keys")) return r;
-        { ProfScope p(TEXGS_K_SORT, s);
-          if (int r = launch_sort(c, geom, bin, s)) return fail("tile sort", (hipError_t)r); }
-        if (int r = check(frame, s, "tile sort")) return r;
+        { ProfScope p(TEXGS_K_DUPLICATE, s); st = launch_duplicate(c, geom, bin, s); }
+        if (int r = launched("duplicate_with_keys", st, s, frame->debug)) return r;
+        { ProfScope p(TEXGS_K_SORT, s); st = launch_sort(c, geom, bin, s); }
+        if (int r = launched("tile sort", st, s, frame->debug)) return r;
     }
     // (the one-workgroup tile-order kernel also zero-fills the per-bin footprint counters K6 adds into)
     { ProfScope p(TEXGS_K_RANGES, s);
-      launch_ranges(c, bin, img->tex_bin_count, img->tex_bin_count ? 2 * (int)tex_bin_count(c.R) : 0, s); }
-    if (int r = check(frame, s, "tile_ranges")) return r;
+      st = launch_ranges(c, bin, img->tex_bin_count, img->tex_bin_count ? 2 * (int)tex_bin_count(c.R) : 0, s); }
+    if (int r = launched("tile_ranges", st, s, frame->debug)) return r;
     return render_forward_impl(frame, in, geom, bin, img, stream, true);
 }
 
@@ -218,11 +212,12 @@ int texgs_backward_render(const TexGSFrame* frame, const TexGSInputs* in, const 
     hipStream_t s = (hipStream_t)stream;
     const CamConst c = make_cam(frame);
     if (bin->num_rendered > 0) {
-        { ProfScope p(TEXGS_K_RENDER_BWD, s); launch_render_bwd(c, frame, in, geom, bin, img, grads, s); }
-        if (int r = check(frame, s, "render_bwd")) return r;
+        hipError_t st;
+        { ProfScope p(TEXGS_K_RENDER_BWD, s); st = launch_render_bwd(c, frame, in, geom, bin, img, grads, s); }
+        if (int r = launched("render_bwd", st, s, frame->debug)) return r;
         if (tex_bins_enabled(c, in, img, grads)) {
-            { ProfScope p(TEXGS_K_TEXGRAD_REDUCE, s); launch_texgrad_reduce(c, img, grads, s); }
-            if (int r = check(frame, s, "texgrad_reduce")) return r;
+            { ProfScope p(TEXGS_K_TEXGRAD_REDUCE, s); st = launch_texgrad_reduce(c, img, grads, s); }
+            return launched("texgrad_reduce", st, s, frame->debug);
         }
     }
     return 0;
@@ -237,8 +232,9 @@ int texgs_backward_preprocess(const TexGSFrame* frame, const TexGSInputs* in, co
     if (in->cov3D_precomp && !grads->dL_dcov3D) return fail_msg("dL_dcov3D is required with cov3D_precomp");
     hipStream_t s = (hipStream_t)stream;
     const CamConst c = make_cam(frame);
-    { ProfScope p(TEXGS_K_PREPROCESS_BWD, s); launch_preprocess_bwd(c, frame, in, geom, grads, s); }
-    return check(frame, s, "preprocess_bwd");
+    hipError_t st;
+    { ProfScope p(TEXGS_K_PREPROCESS_BWD, s); st = launch_preprocess_bwd(c, frame, in, geom, grads, s); }
+    return launched("preprocess_bwd", st, s, frame->debug);
 }
 
 // (Round 5, measured null: the texture-gradient reduce on a side stream next to K8 -- both wait only for K7 -- changed nothing:
@@ -287,10 +283,8 @@ int texgs_rgb_alpha_loss(const float* image, const float* gt_image, const float*
     if (!image || !gt_image || !scratch || !sums || !dL_dimage) return fail_msg("NULL argument");
     if (H <= 0 || W <= 0) return fail_msg("image size must be positive");
     hipStream_t s = (hipStream_t)stream;
-    launch_rgb_alpha_loss(image, gt_image, alpha, gt_alpha, H, W, lambda_dssim, lambda_alpha, scratch, sums, dL_dimage,
-                          dL_dalpha, s);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("rgb_alpha_loss", e);
+    return launched("rgb_alpha_loss", launch_rgb_alpha_loss(image, gt_image, alpha, gt_alpha, H, W, lambda_dssim, lambda_alpha, scratch,
+                                                            sums, dL_dimage, dL_dalpha, s), s, false);
 }
 
 int texgs_geom_losses(const float* norm, const float* gt_norm, const float* gt_image, const float* mask, const float* depth,
@@ -301,19 +295,18 @@ int texgs_geom_losses(const float* norm, const float* gt_norm, const float* gt_i
     if (lambda_norm != 0.f && (!norm || !gt_norm || !dL_dnorm)) return fail_msg("norm term needs norm, gt_norm, dL_dnorm");
     if (lambda_smooth != 0.f && (!norm || !gt_image || !dL_dnorm)) return fail_msg("smoothness term needs norm, gt_image, dL_dnorm");
     if (lambda_depth != 0.f && (!depth || !gt_depth || !dL_ddepth)) return fail_msg("depth term needs depth, gt_depth, dL_ddepth");
-    launch_geom_losses(norm, gt_norm, gt_image, mask, depth, gt_depth, H, W, lambda_norm, lambda_smooth, gamma, lambda_depth, sums,
-                       dL_dnorm, dL_ddepth, (hipStream_t)stream);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("geom_losses", e);
+    hipStream_t s = (hipStream_t)stream;
+    return launched("geom_losses", launch_geom_losses(norm, gt_norm, gt_image, mask, depth, gt_depth, H, W, lambda_norm, lambda_smooth,
+                                                      gamma, lambda_depth, sums, dL_dnorm, dL_ddepth, s), s, false);
 }
 
 int texgs_norm_from_depth(const float* depth, const float* viewmatrix, float tanfovx, float tanfovy, int32_t H, int32_t W,
                           float threshold, float* out_norm, float* out_mask, void* stream) {
     if (!depth || !viewmatrix || !out_norm || !out_mask) return fail_msg("NULL argument");
     if (H <= 0 || W <= 0) return fail_msg("image size must be positive");
-    launch_norm_from_depth(depth, viewmatrix, tanfovx, tanfovy, H, W, threshold, out_norm, out_mask, (hipStream_t)stream);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("norm_from_depth", e);
+    hipStream_t s = (hipStream_t)stream;
+    return launched("norm_from_depth", launch_norm_from_depth(depth, viewmatrix, tanfovx, tanfovy, H, W, threshold, out_norm, out_mask, s),
+                    s, false);
 }
 
 static int check_uvnet(const TexGSUVNet* net, int32_t precision) {
@@ -329,8 +322,8 @@ size_t texgs_uv_packed_bytes(int32_t precision) { return uv_packed_bytes(precisi
 int texgs_uv_pack(const TexGSUVNet* net, int32_t precision, void* packed, void* stream) {
     if (!net || !packed) return fail_msg("NULL argument");
     if (int r = check_uvnet(net, precision)) return r;
-    if (int r = launch_uv_pack(net, precision, packed, (hipStream_t)stream)) return fail("uv_pack", (hipError_t)r);
-    return 0;
+    hipStream_t s = (hipStream_t)stream;
+    return launched("uv_pack", launch_uv_pack(net, precision, packed, s), s, false);
 }
 
 int texgs_uv_taylor_packed(const TexGSUVNet* net, int32_t precision, const void* packed, const float* xyz, int32_t N, float* uvs,
@@ -339,8 +332,8 @@ int texgs_uv_taylor_packed(const TexGSUVNet* net, int32_t precision, const void*
     if (int r = check_uvnet(net, precision)) return r;
     if (N < 0) return fail_msg("N < 0");
     if (N > 0 && (!xyz || !uvs || !grad_uvs)) return fail_msg("NULL argument");   /* (an empty tensor's data pointer is NULL) */
-    if (int r = launch_uv_taylor_packed(net, precision, packed, xyz, N, uvs, grad_uvs, (hipStream_t)stream)) return fail("uv_taylor", (hipError_t)r);
-    return 0;
+    hipStream_t s = (hipStream_t)stream;
+    return launched("uv_taylor", launch_uv_taylor_packed(net, precision, packed, xyz, N, uvs, grad_uvs, s), s, false);
 }
 
 size_t texgs_uv_backward_temp_bytes(int32_t N) { return uv_backward_temp_bytes(N < 0 ? 0 : N); }
@@ -351,9 +344,8 @@ int texgs_uv_backward(const TexGSUVNet* net, int32_t precision, const float* xyz
     if (int r = check_uvnet(net, precision)) return r;
     if (N < 0) return fail_msg("N < 0");
     if (N > 0 && (!xyz || !g_uvs)) return fail_msg("NULL argument");
-    if (int r = launch_uv_backward(net, xyz, g_uvs, N, out, temp, precision != TEXGS_UV_FP32, (hipStream_t)stream))
-        return fail("uv_backward", (hipError_t)r);
-    return 0;
+    hipStream_t s = (hipStream_t)stream;
+    return launched("uv_backward", launch_uv_backward(net, xyz, g_uvs, N, out, temp, precision != TEXGS_UV_FP32, s), s, false);
 }
 
 static int check_hashgrid(const TexGSHashGrid* g, uint32_t* n_params) {
@@ -394,9 +386,8 @@ int texgs_hashgrid_forward(const TexGSHashGrid* grid, const float* params, const
     if ((int64_t)N * grid->n_levels * TEXGS_HASHGRID_FEATURES > INT32_MAX) return fail_msg("N * L * F >= 2^31");
     if (N > 0 && (!params || !x || !enc)) return fail_msg("NULL argument");
     if (N > 0 && (((uintptr_t)params | (uintptr_t)enc) & 15)) return fail_msg("params and enc must be 16-byte aligned");
-    if (int r = launch_hashgrid_forward(grid, params, x, N, enc, (hipStream_t)stream)) return fail("hashgrid_forward", (hipError_t)r);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("hashgrid_forward", e);
+    hipStream_t s = (hipStream_t)stream;
+    return launched("hashgrid_forward", launch_hashgrid_forward(grid, params, x, N, enc, s), s, false);
 }
 
 size_t texgs_hashgrid_backward_temp_bytes(const TexGSHashGrid* grid, int32_t N) {
@@ -415,10 +406,8 @@ int texgs_hashgrid_backward(const TexGSHashGrid* grid, const float* params, cons
     if (N > 0 && (((uintptr_t)params | (uintptr_t)d_enc | (uintptr_t)d_params) & 15))
         return fail_msg("params, d_enc and d_params must be 16-byte aligned");
     if (N > 0 && d_x && !temp) return fail_msg("temp is NULL (d_x needs texgs_hashgrid_backward_temp_bytes)");
-    if (int r = launch_hashgrid_backward(grid, params, x, d_enc, N, d_params, d_x, temp, (hipStream_t)stream))
-        return fail("hashgrid_backward", (hipError_t)r);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("hashgrid_backward", e);
+    hipStream_t s = (hipStream_t)stream;
+    return launched("hashgrid_backward", launch_hashgrid_backward(grid, params, x, d_enc, N, d_params, d_x, temp, s), s, false);
 }
 
 size_t texgs_chamfer_nn_temp_bytes(int32_t P) { return chamfer_nn_temp_bytes(P); }
@@ -428,9 +417,8 @@ int texgs_chamfer_nn(const float* a, int32_t P, const float* b, int32_t Q, float
     if (Q < 1) return fail_msg("the reference set is empty (Q < 1)");
     if ((int64_t)Q > 65535ll * 512) return fail_msg("Q > 65535 * 512");
     if (P > 0 && (!a || !b || !d2 || !idx || !temp)) return fail_msg("NULL argument");
-    if (int r = launch_chamfer_nn(a, P, b, Q, d2, idx, temp, (hipStream_t)stream)) return fail("chamfer_nn", (hipError_t)r);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("chamfer_nn", e);
+    hipStream_t s = (hipStream_t)stream;
+    return launched("chamfer_nn", launch_chamfer_nn(a, P, b, Q, d2, idx, temp, s), s, false);
 }
 
 size_t texgs_knn3_temp_bytes(int32_t n) { return knn3_temp_bytes(n); }
@@ -438,8 +426,8 @@ size_t texgs_knn3_temp_bytes(int32_t n) { return knn3_temp_bytes(n); }
 int texgs_knn3_mean_dist2(const float* xyz, int32_t n, float* mean_d2, void* temp, void* stream) {
     if (n < 4) return fail_msg("n < 4: three nearest other points need at least four points");
     if (!xyz || !mean_d2 || !temp) return fail_msg("NULL argument");
-    if (int r = launch_knn3_mean_dist2(xyz, n, mean_d2, temp, (hipStream_t)stream)) return fail("knn3_mean_dist2", (hipError_t)r);
-    return 0;
+    hipStream_t s = (hipStream_t)stream;
+    return launched("knn3_mean_dist2", launch_knn3_mean_dist2(xyz, n, mean_d2, temp, s), s, false);
 }
 
 size_t texgs_fps_temp_bytes(int32_t n, int32_t k) { return fps_temp_bytes(n, k); }
@@ -449,8 +437,8 @@ int texgs_farthest_points(const float* xyz, int32_t n, int32_t k, int32_t start,
     if (k < 1 || k > n) return fail_msg("k must be in [1, n]");
     if (start < 0 || start >= n) return fail_msg("start must be in [0, n)");
     if (!xyz || !idx || !temp) return fail_msg("NULL argument");
-    if (int r = launch_farthest_points(xyz, n, k, start, idx, temp, (hipStream_t)stream)) return fail("farthest_points", (hipError_t)r);
-    return 0;
+    hipStream_t s = (hipStream_t)stream;
+    return launched("farthest_points", launch_farthest_points(xyz, n, k, start, idx, temp, s), s, false);
 }
 
 static int cube_shape_ok(int32_t R, int32_t C) {
@@ -466,8 +454,8 @@ int texgs_cube_sample(const float* tex, int32_t R, int32_t C, const float* dirs,
     if (N < 0) return fail_msg("N < 0");
     if (filter != TEXGS_CUBE_LINEAR && filter != TEXGS_CUBE_NEAREST) return fail_msg("filter must be TEXGS_CUBE_LINEAR or TEXGS_CUBE_NEAREST");
     if (!tex || (N > 0 && (!dirs || !out))) return fail_msg("NULL argument");
-    if (int r = launch_cube_sample(tex, R, C, dirs, N, filter, tap_map, out, (hipStream_t)stream)) return fail("cube_sample", (hipError_t)r);
-    return 0;
+    hipStream_t s = (hipStream_t)stream;
+    return launched("cube_sample", launch_cube_sample(tex, R, C, dirs, N, filter, tap_map, out, s), s, false);
 }
 
 int texgs_cube_latlong(const float* tex, int32_t R, int32_t C, int32_t H, int32_t W, int32_t tap_map, float* out, void* stream) {
@@ -475,8 +463,8 @@ int texgs_cube_latlong(const float* tex, int32_t R, int32_t C, int32_t H, int32_
     if (H < 1 || W < 1) return fail_msg("H and W must be positive");
     if ((long long)H * W >= (1ll << 31)) return fail_msg("H W must be below 2^31");
     if (!tex || !out) return fail_msg("NULL argument");
-    if (int r = launch_cube_latlong(tex, R, C, H, W, tap_map, out, (hipStream_t)stream)) return fail("cube_latlong", (hipError_t)r);
-    return 0;
+    hipStream_t s = (hipStream_t)stream;
+    return launched("cube_latlong", launch_cube_latlong(tex, R, C, H, W, tap_map, out, s), s, false);
 }
 
 int texgs_cube_sample_backward(const float* tex, int32_t R, int32_t C, const float* dirs, int32_t N, const float* g_out,
@@ -485,9 +473,8 @@ int texgs_cube_sample_backward(const float* tex, int32_t R, int32_t C, const flo
     if (N < 0) return fail_msg("N < 0");
     if (!d_tex && !d_dirs) return fail_msg("d_tex and d_dirs are both NULL: nothing to compute");
     if ((d_dirs && !tex) || (N > 0 && (!dirs || !g_out))) return fail_msg("NULL argument");
-    if (int r = launch_cube_sample_backward(tex, R, C, dirs, N, g_out, d_tex, d_dirs, (hipStream_t)stream))
-        return fail("cube_sample_backward", (hipError_t)r);
-    return 0;
+    hipStream_t s = (hipStream_t)stream;
+    return launched("cube_sample_backward", launch_cube_sample_backward(tex, R, C, dirs, N, g_out, d_tex, d_dirs, s), s, false);
 }
 
 int texgs_cube_sample_nearest_backward(int32_t R, int32_t C, const float* dirs, int32_t N, const float* g_out, float* d_tex,
@@ -495,16 +482,15 @@ int texgs_cube_sample_nearest_backward(int32_t R, int32_t C, const float* dirs, 
     if (int r = cube_shape_ok(R, C)) return r;
     if (N < 0) return fail_msg("N < 0");
     if (!d_tex || (N > 0 && (!dirs || !g_out))) return fail_msg("NULL argument");
-    if (int r = launch_cube_sample_nearest_backward(R, C, dirs, N, g_out, d_tex, (hipStream_t)stream))
-        return fail("cube_sample_nearest_backward", (hipError_t)r);
-    return 0;
+    hipStream_t s = (hipStream_t)stream;
+    return launched("cube_sample_nearest_backward", launch_cube_sample_nearest_backward(R, C, dirs, N, g_out, d_tex, s), s, false);
 }
 
 int texgs_density_stats(const float* grad, const int32_t* radii, int32_t n, float* accum, float* denom, float* max_radii, void* stream) {
     if (n < 0) return fail_msg("n < 0");
     if (n > 0 && (!grad || !radii || !accum || !denom || !max_radii)) return fail_msg("NULL argument");
-    if (int r = launch_density_stats(grad, radii, n, accum, denom, max_radii, (hipStream_t)stream)) return fail("density_stats", (hipError_t)r);
-    return 0;
+    hipStream_t s = (hipStream_t)stream;
+    return launched("density_stats", launch_density_stats(grad, radii, n, accum, denom, max_radii, s), s, false);
 }
 
 size_t texgs_density_plan_temp_bytes(int32_t n) { return density_plan_temp_bytes(n); }
@@ -515,8 +501,8 @@ int texgs_density_plan(const TexGSDensityPlan* plan, uint8_t* action, int32_t* r
     if (plan->n > 0 && (!plan->scaling || !plan->opacity || !action || !rank || !temp)) return fail_msg("NULL argument");
     if (plan->n > 0 && plan->densify && (!plan->accum || !plan->denom)) return fail_msg("accum and denom are required to densify");
     if (plan->densify && !(plan->max_grad > 0.0f)) return fail_msg("max_grad must be positive (with 0 the reference splits its own clones)");
-    if (int r = launch_density_plan(plan, action, rank, totals, temp, (hipStream_t)stream)) return fail("density_plan", (hipError_t)r);
-    return 0;
+    hipStream_t s = (hipStream_t)stream;
+    return launched("density_plan", launch_density_plan(plan, action, rank, totals, temp, s), s, false);
 }
 
 int texgs_density_move(const TexGSDensityMove* m, void* stream) {
@@ -538,8 +524,7 @@ int texgs_density_move(const TexGSDensityMove* m, void* stream) {
             return fail_msg("an XYZ row with children needs scaling, rotation and noise");
     }
     if (!out_rows) return 0;        // everything pruned: there is no row to write
-    if (int r = launch_density_move(m, (hipStream_t)stream)) return fail("density_move", (hipError_t)r);
-    return 0;
+    return launched("density_move", launch_density_move(m, (hipStream_t)stream), (hipStream_t)stream, false);
 }
 
 size_t texgs_eval_metrics_temp_bytes(int32_t H, int32_t W) { return eval_metrics_temp_bytes(H, W); }
@@ -550,24 +535,20 @@ int texgs_eval_metrics(const float* image, const float* gt_image, const float* n
     if (H < 7 || W < 7) return fail_msg("H and W must be at least 7: the 7x7 SSIM window does not fit");
     if ((!norm) != (!gt_norm)) return fail_msg("norm and gt_norm must be both NULL or both set");
     if ((((int64_t)W + 31) / 32) * (((int64_t)H + 31) / 32) >= (1ll << 31)) return fail_msg("image too large: 2^31 tiles or more");
-    if (int r = launch_eval_metrics(image, gt_image, norm, gt_norm, alpha, H, W, clamp01 != 0, temp, row, (hipStream_t)stream))
-        return fail("eval_metrics", (hipError_t)r);
-    return 0;
+    hipStream_t s = (hipStream_t)stream;
+    return launched("eval_metrics", launch_eval_metrics(image, gt_image, norm, gt_norm, alpha, H, W, clamp01 != 0, temp, row, s), s, false);
 }
 
 int texgs_selftest_waveops(const float* seed128, float* out576, void* stream) {
     if (!seed128 || !out576) return fail_msg("NULL argument");
-    launch_selftest_waveops(seed128, out576, (hipStream_t)stream);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("selftest_waveops", e);
+    return launched("selftest_waveops", launch_selftest_waveops(seed128, out576, (hipStream_t)stream), (hipStream_t)stream, false);
 }
 
 int texgs_mark_visible(const TexGSFrame* frame, const float* means3D, uint8_t* visible, void* stream) {
     if (int r = validate_frame(frame)) return r;
     if (!means3D || !visible) return fail_msg("NULL argument");
     hipStream_t s = (hipStream_t)stream;
-    launch_mark_visible(frame, means3D, visible, s);
-    return check(frame, s, "mark_visible");
+    return launched("mark_visible", launch_mark_visible(frame, means3D, visible, s), s, frame->debug);
 }
 
 }  // extern "C"

@@ -846,8 +846,8 @@ uint32_t* bin_header_ptr(const TexGSGeom* g, int N, int* words) {       // bin t
 // (bits of view z; 0xFFFFFFFF for culled) in g->depth and its per-workgroup (min, max).  Independent of D: runs while the host
 // waits for the D readback.  Result (all in scan_temp): (key_b, val_b) = depth bits / Gaussian index in rank order, loc_b = the
 // prefix inside each rank's sort group; K3 completes it with the scan of the groups' tile sums and writes g->offsets.
-int launch_depth_sort_scan(const TexGSGeom* g, int N, hipStream_t s) {
-    if (N <= 0) return 0;
+hipError_t launch_depth_sort_scan(const TexGSGeom* g, int N, hipStream_t s) {
+    if (N <= 0) return hipSuccess;
     const GaussScratch gs = gauss_scratch(g->scan_temp, N);
     const int nblk = (N + TG_BLOCK - 1) / TG_BLOCK;
     const int blocks = (N + DS_PER - 1) / DS_PER;
@@ -861,12 +861,11 @@ int launch_depth_sort_scan(const TexGSGeom* g, int N, hipStream_t s) {
                        (const uint32_t*)gs.gpos, (const uint32_t*)gs.drange, gs.pair_a, gs.key_b, gs.val_b,
                        (const uint32_t*)g->tiles_touched, gs.loc_b, gs.bsum, gmax);
     if (gmax > DS_FUSED_GROUPS) hipLaunchKernelGGL(k_depth_prefix, dim3(1), dim3(1024), 0, s, (const uint32_t*)gs.drange, gs.bsum);
-    hipError_t e = hipGetLastError();
-    return (int)e;
+    return hipGetLastError();
 }
 
-void launch_duplicate(const CamConst& c, const TexGSGeom* g, TexGSBinning* b, hipStream_t s) {
-    if (c.N <= 0 || b->num_rendered == 0) return;
+hipError_t launch_duplicate(const CamConst& c, const TexGSGeom* g, TexGSBinning* b, hipStream_t s) {
+    if (c.N <= 0 || b->num_rendered == 0) return hipSuccess;
     const GaussScratch gs = gauss_scratch(g->scan_temp, c.N);
     const int blocks = (c.N + TG_BLOCK - 1) / TG_BLOCK;
     const bool pre = depth_max_groups(c.N, 1 << depth_log2_bins(c.N)) > DS_FUSED_GROUPS;       // (launch_depth_sort_scan ran k_depth_prefix)
@@ -876,20 +875,21 @@ void launch_duplicate(const CamConst& c, const TexGSGeom* g, TexGSBinning* b, hi
                        reinterpret_cast<uint32_t*>(b->sort_temp), (int)(zero_header_bytes(TILE_PASSES_MAX, 0) / 4))
     if (pre) K3_LAUNCH(true); else K3_LAUNCH(false);
 #undef K3_LAUNCH
+    return hipGetLastError();
 }
 
 // Instance level: stable LSD sort by tile id in 1-3 digits of at most 8 bits (two for up to 65 536 tiles); the last pass
 // writes keys_sorted / point_list.  With three passes (more than 65 536 tiles, i.e. images beyond ~16 Mpixel) the middle pass
 // uses keys_unsorted as its output buffer: its K3 contents are then gone after the forward.
-int launch_sort(const CamConst& c, const TexGSGeom* g, TexGSBinning* b, hipStream_t s) {
+hipError_t launch_sort(const CamConst& c, const TexGSGeom* g, TexGSBinning* b, hipStream_t s) {
     const uint32_t D = b->num_rendered;
-    if (D == 0) return 0;
+    if (D == 0) return hipSuccess;
     const GaussScratch gs = gauss_scratch(g->scan_temp, c.N);
     uint32_t* tbl = reinterpret_cast<uint32_t*>(b->sort_temp);
     uint64_t* tmp = reinterpret_cast<uint64_t*>((char*)b->sort_temp + sort_tables_bytes());
     const int tb = tile_bits((uint32_t)(c.tiles_x * c.tiles_y));
     const int npass = (tb + 7) / 8;
-    if (npass > TILE_PASSES_MAX) return (int)hipErrorInvalidValue;       // validate_frame rejects such images first
+    if (npass > TILE_PASSES_MAX) return hipErrorInvalidValue;       // validate_frame rejects such images first
     uint32_t blocks, per;
     pass_geometry(D, blocks, per);
     const uint64_t* src = b->keys_unsorted;
@@ -913,7 +913,7 @@ int launch_sort(const CamConst& c, const TexGSGeom* g, TexGSBinning* b, hipStrea
         }
         shift += bits; left -= bits;
     }
-    return (int)hipGetLastError();
+    return hipGetLastError();
 }
 
 // Stable LSD sort of n (u32 key, element index) pairs over the low `key_bits` bits (points.hip: Morton codes) with the same count /
@@ -925,14 +925,14 @@ inline size_t pair_tables_bytes() {
 }
 size_t sort_pairs32_temp_bytes(uint32_t n) { return pair_tables_bytes() + 2 * align256((size_t)(n > 0 ? n : 1) * 4); }
 
-int launch_sort_pairs32(const uint32_t* keys_in, uint32_t n, int key_bits, uint32_t* keys_out, uint32_t* vals_out, void* temp, hipStream_t s) {
-    if (n == 0) return 0;
+hipError_t launch_sort_pairs32(const uint32_t* keys_in, uint32_t n, int key_bits, uint32_t* keys_out, uint32_t* vals_out, void* temp, hipStream_t s) {
+    if (n == 0) return hipSuccess;
     const int npass = (key_bits + 7) / 8;
-    if (key_bits < 1 || npass > PAIR_PASSES_MAX) return (int)hipErrorInvalidValue;
+    if (key_bits < 1 || npass > PAIR_PASSES_MAX) return hipErrorInvalidValue;
     uint32_t* tbl = reinterpret_cast<uint32_t*>(temp);
     uint32_t* tk = reinterpret_cast<uint32_t*>((char*)temp + pair_tables_bytes());
     uint32_t* tv = reinterpret_cast<uint32_t*>((char*)tk + align256((size_t)n * 4));
-    if (hipError_t e = hipMemsetAsync(tbl, 0, zero_header_bytes(PAIR_PASSES_MAX, 0), s)) return (int)e;
+    if (hipError_t e = hipMemsetAsync(tbl, 0, zero_header_bytes(PAIR_PASSES_MAX, 0), s)) return e;
     uint32_t blocks, per;
     pass_geometry(n, blocks, per);
     const uint32_t* sk = keys_in;
@@ -951,12 +951,13 @@ int launch_sort_pairs32(const uint32_t* keys_in, uint32_t n, int key_bits, uint3
         sk = dk; sv = dv;
         shift += bits; left -= bits;
     }
-    return (int)hipGetLastError();
+    return hipGetLastError();
 }
 
-void launch_ranges(const CamConst& c, TexGSBinning* b, uint32_t* zero_words, int num_zero_words, hipStream_t s) {
+hipError_t launch_ranges(const CamConst& c, TexGSBinning* b, uint32_t* zero_words, int num_zero_words, hipStream_t s) {
     const uint32_t T = (uint32_t)(c.tiles_x * c.tiles_y);
-    if (b->num_rendered == 0) (void)hipMemsetAsync(b->ranges, 0, sizeof(uint32_t) * 2 * T, s);     // no K3 ran: every tile is empty
+    LaunchStatus st;
+    if (b->num_rendered == 0) st += hipMemsetAsync(b->ranges, 0, sizeof(uint32_t) * 2 * T, s);     // no K3 ran: every tile is empty
     if (b->num_rendered > 0) {
         const int blocks = (int)((b->num_rendered + TG_BLOCK - 1) / TG_BLOCK);
         hipLaunchKernelGGL(k_ranges, dim3(blocks), dim3(TG_BLOCK), 0, s, b->num_rendered, b->keys_sorted,
@@ -964,4 +965,5 @@ void launch_ranges(const CamConst& c, TexGSBinning* b, uint32_t* zero_words, int
     }
     hipLaunchKernelGGL(k_tile_order, dim3(1), dim3(1024), 0, s, T, reinterpret_cast<const uint2*>(b->ranges), b->tile_order,
                        zero_words, num_zero_words);
+    return st.after_launches();
 }

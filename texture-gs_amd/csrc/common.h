@@ -53,64 +53,73 @@ static inline CamConst make_cam(const TexGSFrame* f) {
     return c;
 }
 
-// launchers implemented in the .hip files (host side, called from abi.hip)
-void launch_preprocess_fwd(const CamConst& c, const TexGSFrame* f, const TexGSInputs* in, TexGSGeom* g, hipStream_t s);
-void launch_preprocess_bwd(const CamConst& c, const TexGSFrame* f, const TexGSInputs* in, const TexGSGeom* g,
+// Status of a launcher that issues more than one runtime call: `st += hipMemsetAsync(...)` keeps the FIRST failure;
+// `return st.after_launches()` adds hipGetLastError(), taken once behind the last launch (which also clears it).
+struct LaunchStatus {
+    hipError_t first = hipSuccess;
+    void operator+=(hipError_t e) { if (first == hipSuccess) first = e; }
+    hipError_t after_launches() { *this += hipGetLastError(); return first; }
+};
+
+// launchers implemented in the .hip files (host side, called from abi.hip): each returns the first failing runtime call it made,
+// else hipGetLastError() behind its last launch
+hipError_t launch_preprocess_fwd(const CamConst& c, const TexGSFrame* f, const TexGSInputs* in, TexGSGeom* g, hipStream_t s);
+hipError_t launch_preprocess_bwd(const CamConst& c, const TexGSFrame* f, const TexGSInputs* in, const TexGSGeom* g,
                            TexGSGrads* gr, hipStream_t s);
-void launch_mark_visible(const TexGSFrame* f, const float* means3D, uint8_t* visible, hipStream_t s);
-int  launch_depth_sort_scan(const TexGSGeom* g, int N, hipStream_t s);
+hipError_t launch_mark_visible(const TexGSFrame* f, const float* means3D, uint8_t* visible, hipStream_t s);
+hipError_t launch_depth_sort_scan(const TexGSGeom* g, int N, hipStream_t s);
 uint32_t* bin_block_sums_ptr(const TexGSGeom* g, int N);
 uint32_t* bin_header_ptr(const TexGSGeom* g, int N, int* words);
 size_t scan_temp_bytes(int N);
 size_t sort_temp_bytes(uint32_t D, uint32_t T);
-void launch_duplicate(const CamConst& c, const TexGSGeom* g, TexGSBinning* b, hipStream_t s);
-int  launch_sort(const CamConst& c, const TexGSGeom* g, TexGSBinning* b, hipStream_t s);
-void launch_ranges(const CamConst& c, TexGSBinning* b, uint32_t* zero_words, int num_zero_words, hipStream_t s);
-void launch_render_fwd(const CamConst& c, const TexGSFrame* f, const TexGSInputs* in, const TexGSGeom* g,
+hipError_t launch_duplicate(const CamConst& c, const TexGSGeom* g, TexGSBinning* b, hipStream_t s);
+hipError_t launch_sort(const CamConst& c, const TexGSGeom* g, TexGSBinning* b, hipStream_t s);
+hipError_t launch_ranges(const CamConst& c, TexGSBinning* b, uint32_t* zero_words, int num_zero_words, hipStream_t s);
+hipError_t launch_render_fwd(const CamConst& c, const TexGSFrame* f, const TexGSInputs* in, const TexGSGeom* g,
                        const TexGSBinning* b, TexGSImage* img, hipStream_t s);
 size_t tex_bin_count(int R);
 bool tex_bins_enabled(const CamConst& c, const TexGSInputs* in, const TexGSImage* img, const TexGSGrads* gr);
-void launch_texgrad_reduce(const CamConst& c, const TexGSImage* img, TexGSGrads* gr, hipStream_t s);
-void launch_render_bwd(const CamConst& c, const TexGSFrame* f, const TexGSInputs* in, const TexGSGeom* g,
+hipError_t launch_texgrad_reduce(const CamConst& c, const TexGSImage* img, TexGSGrads* gr, hipStream_t s);
+hipError_t launch_render_bwd(const CamConst& c, const TexGSFrame* f, const TexGSInputs* in, const TexGSGeom* g,
                        const TexGSBinning* b, const TexGSImage* img, TexGSGrads* gr, hipStream_t s);
-int launch_rgb_alpha_loss(const float* image, const float* gt_image, const float* alpha, const float* gt_alpha, int H,
+hipError_t launch_rgb_alpha_loss(const float* image, const float* gt_image, const float* alpha, const float* gt_alpha, int H,
                           int W, float lambda_dssim, float lambda_alpha, float* scratch, float* sums, float* d_image,
                           float* d_alpha, hipStream_t s);
-void launch_selftest_waveops(const float* seed128, float* out576, hipStream_t s);
-int launch_geom_losses(const float* norm, const float* gt_norm, const float* gt_image, const float* mask, const float* depth,
+hipError_t launch_selftest_waveops(const float* seed128, float* out576, hipStream_t s);
+hipError_t launch_geom_losses(const float* norm, const float* gt_norm, const float* gt_image, const float* mask, const float* depth,
                        const float* gt_depth, int H, int W, float lambda_norm, float lambda_smooth, float gamma,
                        float lambda_depth, float* sums, float* d_norm, float* d_depth, hipStream_t s);
-int launch_norm_from_depth(const float* depth, const float* viewmatrix, float tanfovx, float tanfovy, int H, int W, float threshold,
+hipError_t launch_norm_from_depth(const float* depth, const float* viewmatrix, float tanfovx, float tanfovy, int H, int W, float threshold,
                            float* out_norm, float* out_mask, hipStream_t s);
 size_t uv_packed_bytes(int precision);          // precision: TEXGS_UV_FP32 / _BF16X3 / _MIXED, validated by the caller
-int launch_uv_pack(const TexGSUVNet* net, int precision, void* packed, hipStream_t s);
-int launch_uv_taylor_packed(const TexGSUVNet* net, int precision, const void* packed, const float* xyz, int N, float* uvs, float* grad_uvs,
+hipError_t launch_uv_pack(const TexGSUVNet* net, int precision, void* packed, hipStream_t s);
+hipError_t launch_uv_taylor_packed(const TexGSUVNet* net, int precision, const void* packed, const float* xyz, int N, float* uvs, float* grad_uvs,
                             hipStream_t s);
 size_t uv_backward_temp_bytes(int N);
-int launch_uv_backward(const TexGSUVNet* net, const float* xyz, const float* g, int N, const TexGSUVNetGrad* out, void* temp, int mixed,
+hipError_t launch_uv_backward(const TexGSUVNet* net, const float* xyz, const float* g, int N, const TexGSUVNetGrad* out, void* temp, int mixed,
                        hipStream_t s);
 int hashgrid_levels(const TexGSHashGrid* g, float* scale, uint32_t* res, uint32_t* size, uint32_t* offset, uint32_t* n_params);
-int launch_hashgrid_forward(const TexGSHashGrid* g, const float* params, const float* x, int N, float* enc, hipStream_t s);
+hipError_t launch_hashgrid_forward(const TexGSHashGrid* g, const float* params, const float* x, int N, float* enc, hipStream_t s);
 size_t hashgrid_backward_temp_bytes(const TexGSHashGrid* g, int N);
-int launch_hashgrid_backward(const TexGSHashGrid* g, const float* params, const float* x, const float* d_enc, int N, float* d_params,
+hipError_t launch_hashgrid_backward(const TexGSHashGrid* g, const float* params, const float* x, const float* d_enc, int N, float* d_params,
                              float* d_x, void* temp, hipStream_t s);
 size_t chamfer_nn_temp_bytes(int P);
-int launch_chamfer_nn(const float* a, int P, const float* b, int Q, float* d2, int32_t* idx, void* temp, hipStream_t s);
+hipError_t launch_chamfer_nn(const float* a, int P, const float* b, int Q, float* d2, int32_t* idx, void* temp, hipStream_t s);
 size_t sort_pairs32_temp_bytes(uint32_t n);
-int launch_sort_pairs32(const uint32_t* keys_in, uint32_t n, int key_bits, uint32_t* keys_out, uint32_t* vals_out, void* temp, hipStream_t s);
+hipError_t launch_sort_pairs32(const uint32_t* keys_in, uint32_t n, int key_bits, uint32_t* keys_out, uint32_t* vals_out, void* temp, hipStream_t s);
 size_t knn3_temp_bytes(int n);
-int launch_knn3_mean_dist2(const float* xyz, int n, float* mean_d2, void* temp, hipStream_t s);
+hipError_t launch_knn3_mean_dist2(const float* xyz, int n, float* mean_d2, void* temp, hipStream_t s);
 size_t fps_temp_bytes(int n, int k);
-int launch_farthest_points(const float* xyz, int n, int k, int start, int32_t* idx, void* temp, hipStream_t s);
-int launch_cube_sample(const float* tex, int R, int C, const float* dirs, int N, int filter, int tap_map, float* out, hipStream_t s);
-int launch_cube_latlong(const float* tex, int R, int C, int H, int W, int tap_map, float* out, hipStream_t s);
-int launch_cube_sample_backward(const float* tex, int R, int C, const float* dirs, int N, const float* g_out, float* d_tex,
+hipError_t launch_farthest_points(const float* xyz, int n, int k, int start, int32_t* idx, void* temp, hipStream_t s);
+hipError_t launch_cube_sample(const float* tex, int R, int C, const float* dirs, int N, int filter, int tap_map, float* out, hipStream_t s);
+hipError_t launch_cube_latlong(const float* tex, int R, int C, int H, int W, int tap_map, float* out, hipStream_t s);
+hipError_t launch_cube_sample_backward(const float* tex, int R, int C, const float* dirs, int N, const float* g_out, float* d_tex,
                                 float* d_dirs, hipStream_t s);
-int launch_cube_sample_nearest_backward(int R, int C, const float* dirs, int N, const float* g_out, float* d_tex, hipStream_t s);
-int launch_density_stats(const float* grad, const int32_t* radii, int n, float* accum, float* denom, float* max_radii, hipStream_t s);
+hipError_t launch_cube_sample_nearest_backward(int R, int C, const float* dirs, int N, const float* g_out, float* d_tex, hipStream_t s);
+hipError_t launch_density_stats(const float* grad, const int32_t* radii, int n, float* accum, float* denom, float* max_radii, hipStream_t s);
 size_t density_plan_temp_bytes(int n);
-int launch_density_plan(const TexGSDensityPlan* p, uint8_t* action, int32_t* rank, uint32_t* totals, void* temp, hipStream_t s);
-int launch_density_move(const TexGSDensityMove* m, hipStream_t s);
+hipError_t launch_density_plan(const TexGSDensityPlan* p, uint8_t* action, int32_t* rank, uint32_t* totals, void* temp, hipStream_t s);
+hipError_t launch_density_move(const TexGSDensityMove* m, hipStream_t s);
 size_t eval_metrics_temp_bytes(int H, int W);
-int launch_eval_metrics(const float* image, const float* gt_image, const float* norm, const float* gt_norm, const float* alpha, int H,
+hipError_t launch_eval_metrics(const float* image, const float* gt_image, const float* norm, const float* gt_norm, const float* alpha, int H,
                         int W, int clamp01, void* temp, double* row, hipStream_t s);

@@ -228,29 +228,29 @@ __global__ __launch_bounds__(CT_BLOCK) void k_cube_nearest_bwd(int R, int C, con
 
 static inline uint32_t ct_blocks(long long n) { return (uint32_t)((n + CT_BLOCK - 1) / CT_BLOCK); }
 
-int launch_cube_sample(const float* tex, int R, int C, const float* dirs, int N, int filter, int tap_map, float* out, hipStream_t s) {
-    if (N == 0) return 0;
+hipError_t launch_cube_sample(const float* tex, int R, int C, const float* dirs, int N, int filter, int tap_map, float* out, hipStream_t s) {
+    if (N == 0) return hipSuccess;
     if (tap_map) hipLaunchKernelGGL(k_cube_sample<true>, dim3(ct_blocks(N)), dim3(CT_BLOCK), 0, s, tex, R, C, dirs, N, filter, out);
     else         hipLaunchKernelGGL(k_cube_sample<false>, dim3(ct_blocks(N)), dim3(CT_BLOCK), 0, s, tex, R, C, dirs, N, filter, out);
-    return (int)hipGetLastError();
+    return hipGetLastError();
 }
 
-int launch_cube_latlong(const float* tex, int R, int C, int H, int W, int tap_map, float* out, hipStream_t s) {
+hipError_t launch_cube_latlong(const float* tex, int R, int C, int H, int W, int tap_map, float* out, hipStream_t s) {
     const uint32_t nb = ct_blocks((long long)H * W);
     if (tap_map) hipLaunchKernelGGL(k_cube_latlong<true>, dim3(nb), dim3(CT_BLOCK), 0, s, tex, R, C, H, W, out);
     else         hipLaunchKernelGGL(k_cube_latlong<false>, dim3(nb), dim3(CT_BLOCK), 0, s, tex, R, C, H, W, out);
-    return (int)hipGetLastError();
+    return hipGetLastError();
 }
 
-int launch_cube_sample_backward(const float* tex, int R, int C, const float* dirs, int N, const float* g_out, float* d_tex,
+hipError_t launch_cube_sample_backward(const float* tex, int R, int C, const float* dirs, int N, const float* g_out, float* d_tex,
                                 float* d_dirs, hipStream_t s) {
-    if (N == 0) return 0;
+    if (N == 0) return hipSuccess;
     hipLaunchKernelGGL(k_cube_sample_bwd, dim3(ct_blocks(N)), dim3(CT_BLOCK), 0, s, tex, R, C, dirs, N, g_out, d_tex, d_dirs);
-    return (int)hipGetLastError();
+    return hipGetLastError();
 }
 
-int launch_cube_sample_nearest_backward(int R, int C, const float* dirs, int N, const float* g_out, float* d_tex, hipStream_t s) {
-    if (N == 0) return 0;
+hipError_t launch_cube_sample_nearest_backward(int R, int C, const float* dirs, int N, const float* g_out, float* d_tex, hipStream_t s) {
+    if (N == 0) return hipSuccess;
     hipLaunchKernelGGL(k_cube_nearest_bwd, dim3(ct_blocks(N)), dim3(CT_BLOCK), 0, s, R, C, dirs, N, g_out, d_tex);
-    return (int)hipGetLastError();
+    return hipGetLastError();
 }

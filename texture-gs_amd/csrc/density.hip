@@ -254,11 +254,11 @@ inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 }  // namespace
 
-int launch_density_stats(const float* grad, const int32_t* radii, int n, float* accum, float* denom, float* max_radii, hipStream_t s) {
-    if (n == 0) return 0;
+hipError_t launch_density_stats(const float* grad, const int32_t* radii, int n, float* accum, float* denom, float* max_radii, hipStream_t s) {
+    if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(k_density_stats, dim3(((uint32_t)n + DN_BLOCK - 1) / DN_BLOCK), dim3(DN_BLOCK), 0, s, grad, radii, (uint32_t)n, accum,
                        denom, max_radii);
-    return (int)hipGetLastError();
+    return hipGetLastError();
 }
 
 size_t density_plan_temp_bytes(int n) {
@@ -266,9 +266,9 @@ size_t density_plan_temp_bytes(int n) {
     return align256(tiles * DN_CH * sizeof(uint32_t));
 }
 
-int launch_density_plan(const TexGSDensityPlan* p, uint8_t* action, int32_t* rank, uint32_t* totals, void* temp, hipStream_t s) {
+hipError_t launch_density_plan(const TexGSDensityPlan* p, uint8_t* action, int32_t* rank, uint32_t* totals, void* temp, hipStream_t s) {
     const uint32_t n = (uint32_t)p->n;
-    if (n == 0) return (int)hipMemsetAsync(totals, 0, DN_CH * sizeof(uint32_t), s);
+    if (n == 0) return hipMemsetAsync(totals, 0, DN_CH * sizeof(uint32_t), s);
     const uint32_t tiles = (n + DN_TILE - 1) / DN_TILE;
     PlanArgs a;
     a.accum = p->accum; a.denom = p->denom; a.scaling = p->scaling; a.opacity = p->opacity; a.n = n;
@@ -278,24 +278,24 @@ int launch_density_plan(const TexGSDensityPlan* p, uint8_t* action, int32_t* ran
     hipLaunchKernelGGL(k_density_classify, dim3(tiles), dim3(DN_BLOCK), 0, s, a, action, tile_counts);
     hipLaunchKernelGGL(k_density_scan_tiles, dim3(1), dim3(DN_BLOCK), 0, s, tile_counts, tiles, totals);
     hipLaunchKernelGGL(k_density_ranks, dim3(tiles), dim3(DN_BLOCK), 0, s, (const uint8_t*)action, n, (const uint32_t*)tile_counts, rank);
-    return (int)hipGetLastError();
+    return hipGetLastError();
 }
 
-int launch_density_move(const TexGSDensityMove* m, hipStream_t s) {
+hipError_t launch_density_move(const TexGSDensityMove* m, hipStream_t s) {
     MoveArgs a;
     unsigned long long blocks = 0;
     for (int d = 0; d < m->rows; ++d) {
         a.row[d] = m->row[d];
         a.first_block[d] = (uint32_t)blocks;
         blocks += ((unsigned long long)(uint32_t)m->n * (uint32_t)m->row[d].width + DN_BLOCK - 1) / DN_BLOCK;
-        if (blocks >= (1ull << 31)) return (int)hipErrorInvalidValue;
+        if (blocks >= (1ull << 31)) return hipErrorInvalidValue;
     }
     for (int d = m->rows; d <= DN_MAX_ROWS; ++d) a.first_block[d] = (uint32_t)blocks;
     for (int d = m->rows; d < DN_MAX_ROWS; ++d) a.row[d] = TexGSDensityRow{nullptr, nullptr, 1, TEXGS_DENSITY_ROW_COPY};
     a.rows = m->rows; a.n = (uint32_t)m->n; a.action = m->action; a.rank = m->rank;
     a.n_kept = (uint32_t)m->n_kept; a.n_clone = (uint32_t)m->n_clone; a.n_split = (uint32_t)m->n_split; a.n_child = (uint32_t)m->n_child;
     a.scaling = m->scaling; a.rotation = m->rotation; a.noise = m->noise;
-    if (blocks == 0) return 0;
+    if (blocks == 0) return hipSuccess;
     hipLaunchKernelGGL(k_density_move, dim3((uint32_t)blocks), dim3(DN_BLOCK), 0, s, a);
-    return (int)hipGetLastError();
+    return hipGetLastError();
 }

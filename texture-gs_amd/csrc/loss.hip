@@ -313,31 +313,33 @@ k_norm_from_depth(DepthNormArgs a, const float* __restrict__ viewmatrix, const f
 
 }  // namespace
 
-int launch_geom_losses(const float* norm, const float* gt_norm, const float* gt_image, const float* mask, const float* depth,
+hipError_t launch_geom_losses(const float* norm, const float* gt_norm, const float* gt_image, const float* mask, const float* depth,
                        const float* gt_depth, int H, int W, float lambda_norm, float lambda_smooth, float gamma,
                        float lambda_depth, float* sums, float* d_norm, float* d_depth, hipStream_t s) {
     GeomArgs a;
     a.H = H; a.W = W; a.norm = norm; a.gt_norm = gt_norm; a.gt_image = gt_image; a.mask = mask; a.depth = depth;
     a.gt_depth = gt_depth; a.inv_gamma = 1.f / gamma;
-    (void)hipMemsetAsync(sums, 0, 12 * sizeof(float), s);
+    LaunchStatus st;
+    st += hipMemsetAsync(sums, 0, 12 * sizeof(float), s);
     const int P = H * W, blocks = (P + 255) / 256;
     // 512 persistent blocks (2 per CU) stride over the image: 11 atomics per BLOCK, not per 256 pixels
     hipLaunchKernelGGL(k_geom_sums, dim3(blocks < 512 ? blocks : 512), dim3(256), 0, s, a, lambda_norm != 0.f, lambda_smooth != 0.f,
                        lambda_depth != 0.f, sums);
     hipLaunchKernelGGL(k_geom_grad, dim3(blocks), dim3(256), 0, s, a, lambda_norm, lambda_smooth, lambda_depth,
                        (const float*)sums, d_norm, d_depth);
-    return 0;
+    return st.after_launches();
 }
 
-// returns 0; sums[0..2] = sum|I-Igt|, sum SSIM, sum|A-Agt| (device); dL/dI and dL/dA are for d(loss) = 1
-int launch_rgb_alpha_loss(const float* image, const float* gt_image, const float* alpha, const float* gt_alpha, int H,
+// sums[0..2] = sum|I-Igt|, sum SSIM, sum|A-Agt| (device); dL/dI and dL/dA are for d(loss) = 1
+hipError_t launch_rgb_alpha_loss(const float* image, const float* gt_image, const float* alpha, const float* gt_alpha, int H,
                           int W, float lambda_dssim, float lambda_alpha, float* scratch, float* sums, float* d_image,
                           float* d_alpha, hipStream_t s) {
     Win win;
     float tot = 0.f;
     for (int k = 0; k < 11; ++k) { win.w[k] = expf(-(float)((k - 5) * (k - 5)) / (2.f * 1.5f * 1.5f)); tot += win.w[k]; }
     for (int k = 0; k < 11; ++k) win.w[k] /= tot;
-    (void)hipMemsetAsync(sums, 0, 4 * sizeof(float), s);
+    LaunchStatus st;
+    st += hipMemsetAsync(sums, 0, 4 * sizeof(float), s);
     const dim3 grid((W + LT - 1) / LT, (H + LT - 1) / LT, 3);
     const float n = (float)(3 * (size_t)H * W);
     const int nwork = (int)(grid.x * grid.y * 3);
@@ -351,15 +353,15 @@ int launch_rgb_alpha_loss(const float* image, const float* gt_image, const float
         hipLaunchKernelGGL(k_alpha_l1, dim3(ab < 512 ? ab : 512), dim3(256), 0, s, P, alpha, gt_alpha, lambda_alpha / (float)P,
                            d_alpha, sums);
     }
-    return 0;
+    return st.after_launches();
 }
 
-int launch_norm_from_depth(const float* depth, const float* viewmatrix, float tanfovx, float tanfovy, int H, int W, float threshold,
+hipError_t launch_norm_from_depth(const float* depth, const float* viewmatrix, float tanfovx, float tanfovy, int H, int W, float threshold,
                            float* out_norm, float* out_mask, hipStream_t s) {
     DepthNormArgs a;
     a.H = H; a.W = W; a.tx = tanfovx; a.ty = tanfovy; a.thr = threshold;
     for (int k = 0; k < 12; ++k) a.m[k] = 0.f;
     const int P = H * W;
     hipLaunchKernelGGL(k_norm_from_depth, dim3((P + 255) / 256), dim3(256), 0, s, a, viewmatrix, depth, out_norm, out_mask);
-    return 0;
+    return hipGetLastError();
 }

@@ -173,11 +173,11 @@ size_t eval_metrics_temp_bytes(int H, int W) {
 }
 
 // H, W >= 7, the tile count below 2^31 and the pointers are the caller's (abi.hip) to check
-int launch_eval_metrics(const float* image, const float* gt_image, const float* norm, const float* gt_norm, const float* alpha, int H,
+hipError_t launch_eval_metrics(const float* image, const float* gt_image, const float* norm, const float* gt_norm, const float* alpha, int H,
                         int W, int clamp01, void* temp, double* row, hipStream_t s) {
     const int tiles_x = (W + MT - 1) / MT, nblocks = (int)metrics_blocks(H, W);
     hipLaunchKernelGGL(k_metrics, dim3(nblocks), dim3(256), 0, s, H, W, tiles_x, nblocks, clamp01, image, gt_image, norm, gt_norm,
                        alpha, (double*)temp);
     hipLaunchKernelGGL(k_metrics_reduce, dim3(1), dim3(256), 0, s, H, W, nblocks, (const double*)temp, row);
-    return (int)hipGetLastError();
+    return hipGetLastError();
 }

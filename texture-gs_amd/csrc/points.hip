@@ -343,18 +343,18 @@ KnnTemp knn_temp(void* base, uint32_t n) {
 
 size_t knn3_temp_bytes(int n) { return knn_temp(nullptr, (uint32_t)(n > 0 ? n : 1)).bytes; }
 
-int launch_knn3_mean_dist2(const float* xyz, int n_, float* mean_d2, void* temp, hipStream_t s) {
+hipError_t launch_knn3_mean_dist2(const float* xyz, int n_, float* mean_d2, void* temp, hipStream_t s) {
     const uint32_t n = (uint32_t)n_;
     const KnnTemp t = knn_temp(temp, n);
     const uint32_t nb = (n + PT_BLOCK - 1) / PT_BLOCK;
-    if (hipError_t e = hipMemsetAsync(t.bbox, 0, 256, s)) return (int)e;
+    if (hipError_t e = hipMemsetAsync(t.bbox, 0, 256, s)) return e;
     hipLaunchKernelGGL(k_pt_bbox, dim3(nb < (uint32_t)PT_BBOX_BLOCKS ? nb : (uint32_t)PT_BBOX_BLOCKS), dim3(PT_BLOCK), 0, s, xyz, n, t.bbox);
     hipLaunchKernelGGL(k_pt_morton, dim3(nb), dim3(PT_BLOCK), 0, s, xyz, n, (const uint32_t*)t.bbox, t.codes);
-    if (int r = launch_sort_pairs32(t.codes, n, 30, t.skeys, t.sidx, t.sort, s)) return r;
+    if (hipError_t e = launch_sort_pairs32(t.codes, n, 30, t.skeys, t.sidx, t.sort, s)) return e;
     hipLaunchKernelGGL(k_pt_boxes, dim3(nb), dim3(PT_BLOCK), 0, s, xyz, (const uint32_t*)t.sidx, n, t.sx, t.sy, t.sz, t.bounds);
     hipLaunchKernelGGL(k_pt_search, dim3(nb), dim3(PT_BLOCK), 0, s, (const float*)t.sx, (const float*)t.sy, (const float*)t.sz,
                        (const uint32_t*)t.sidx, (const float*)t.bounds, n, nb, mean_d2);
-    return (int)hipGetLastError();
+    return hipGetLastError();
 }
 
 // temp: m, px, py, pz (n floats each, padded to 256 bytes: a multiple of 4 points), then k x FPS_SUB 64-bit slots
@@ -362,7 +362,7 @@ size_t fps_temp_bytes(int n, int k) {
     return 4 * align256((size_t)(n > 0 ? n : 1) * 4) + align256((size_t)(k > 0 ? k : 1) * 8 * FPS_SUB);
 }
 
-int launch_farthest_points(const float* xyz, int n_, int k_, int start, int32_t* idx, void* temp, hipStream_t s) {
+hipError_t launch_farthest_points(const float* xyz, int n_, int k_, int start, int32_t* idx, void* temp, hipStream_t s) {
     const uint32_t n = (uint32_t)n_, k = (uint32_t)k_;
     const size_t plane = align256((size_t)n * 4);
     float* m = (float*)temp;
@@ -370,7 +370,7 @@ int launch_farthest_points(const float* xyz, int n_, int k_, int start, int32_t*
     float* py = (float*)((char*)temp + 2 * plane);
     float* pz = (float*)((char*)temp + 3 * plane);
     unsigned long long* slots = (unsigned long long*)((char*)temp + 4 * plane);
-    if (hipError_t e = hipMemsetAsync(slots, 0, (size_t)k * 8 * FPS_SUB, s)) return (int)e;
+    if (hipError_t e = hipMemsetAsync(slots, 0, (size_t)k * 8 * FPS_SUB, s)) return e;
     if (k > 1) hipLaunchKernelGGL(k_fps_planes, dim3((n + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, s, xyz, n, px, py, pz);
     const uint32_t grid = (n + PT_BLOCK * FPS_PPL - 1) / (PT_BLOCK * FPS_PPL);
     for (uint32_t t = 1; t < k; ++t) {
@@ -383,7 +383,7 @@ int launch_farthest_points(const float* xyz, int n_, int k_, int start, int32_t*
     }
     hipLaunchKernelGGL(k_fps_unpack, dim3((k + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, s, (const unsigned long long*)slots, k,
                        (uint32_t)start, idx);
-    return (int)hipGetLastError();
+    return hipGetLastError();
 }
 
 #ifdef TEXGS_POINTS_STATS

@@ -711,8 +711,8 @@ k_mark_visible(int N, const float* __restrict__ vm, const float* __restrict__ me
 
 }  // namespace
 
-void launch_preprocess_fwd(const CamConst& c, const TexGSFrame* f, const TexGSInputs* in, TexGSGeom* g, hipStream_t s) {
-    if (c.N <= 0) return;
+hipError_t launch_preprocess_fwd(const CamConst& c, const TexGSFrame* f, const TexGSInputs* in, TexGSGeom* g, hipStream_t s) {
+    if (c.N <= 0) return hipSuccess;
     const int blocks = (c.N + TG_BLOCK - 1) / TG_BLOCK;
     const size_t lds = (in->shs && c.sh_degree > 0) ? (size_t)TG_BLOCK * 3 * c.sh_coeffs * sizeof(float) : 0;
     int hdr_words = 0;
@@ -723,11 +723,12 @@ void launch_preprocess_fwd(const CamConst& c, const TexGSFrame* f, const TexGSIn
                        reinterpret_cast<uint2*>(g->rect), g->tiles_touched, bin_block_sums_ptr(g, c.N), hdr, hdr_words)
     if (in->cov3D_precomp) K1_LAUNCH(true); else K1_LAUNCH(false);
 #undef K1_LAUNCH
+    return hipGetLastError();
 }
 
-void launch_preprocess_bwd(const CamConst& c, const TexGSFrame* f, const TexGSInputs* in, const TexGSGeom* g,
+hipError_t launch_preprocess_bwd(const CamConst& c, const TexGSFrame* f, const TexGSInputs* in, const TexGSGeom* g,
                            TexGSGrads* gr, hipStream_t s) {
-    if (c.N <= 0) return;
+    if (c.N <= 0) return hipSuccess;
     const int blocks = (c.N + K8_BLOCK - 1) / K8_BLOCK;
     const size_t lds = gr->dL_dshs ? (size_t)K8_BLOCK * 3 * c.sh_coeffs * sizeof(float) : 0;
 #define K8_LAUNCH(COV) hipLaunchKernelGGL(k_preprocess_bwd<COV>, dim3(blocks), dim3(K8_BLOCK), lds, s, c, f->viewmatrix, f->projmatrix, f->campos, \
@@ -736,10 +737,12 @@ void launch_preprocess_bwd(const CamConst& c, const TexGSFrame* f, const TexGSIn
                        gr->dL_drotations, gr->dL_duvs, gr->dL_dcolor_offset, gr->dL_dcov3D, gr->accumulate)
     if (in->cov3D_precomp) K8_LAUNCH(true); else K8_LAUNCH(false);
 #undef K8_LAUNCH
+    return hipGetLastError();
 }
 
-void launch_mark_visible(const TexGSFrame* f, const float* means3D, uint8_t* visible, hipStream_t s) {
-    if (f->num_gaussians <= 0) return;
+hipError_t launch_mark_visible(const TexGSFrame* f, const float* means3D, uint8_t* visible, hipStream_t s) {
+    if (f->num_gaussians <= 0) return hipSuccess;
     const int blocks = (f->num_gaussians + TG_BLOCK - 1) / TG_BLOCK;
     hipLaunchKernelGGL(k_mark_visible, dim3(blocks), dim3(TG_BLOCK), 0, s, f->num_gaussians, f->viewmatrix, means3D, visible);
+    return hipGetLastError();
 }

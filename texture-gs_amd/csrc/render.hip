@@ -856,7 +856,7 @@ size_t tex_bin_count(int R) {
     return 6 * nb * nb;
 }
 
-void launch_render_fwd(const CamConst& c, const TexGSFrame* f, const TexGSInputs* in, const TexGSGeom* g,
+hipError_t launch_render_fwd(const CamConst& c, const TexGSFrame* f, const TexGSInputs* in, const TexGSGeom* g,
                        const TexGSBinning* b, TexGSImage* img, hipStream_t s) {
     const PixArgs a = make_pix(c, f, in, g, b, img);
     if (in->texture)
@@ -865,19 +865,20 @@ void launch_render_fwd(const CamConst& c, const TexGSFrame* f, const TexGSInputs
     else
         hipLaunchKernelGGL(k_render_fwd<false>, dim3(blend_grid(a.num_tiles)), dim3(64), 0, s, a, img->out_color, img->out_depth,
                            img->out_norm, img->out_alpha, img->final_T, img->n_contrib, (uint32_t*)nullptr);
+    return hipGetLastError();
 }
 
 // Which flavour of K7 a call gets (see the template's comment): the texture gradient only when it is wanted and there is a texture,
 // the per-Gaussian stages only when a Gaussian gradient is wanted; the UV chain rides with the per-Gaussian stages of the textured
 // operator.
-void launch_render_bwd(const CamConst& c, const TexGSFrame* f, const TexGSInputs* in, const TexGSGeom* g,
+hipError_t launch_render_bwd(const CamConst& c, const TexGSFrame* f, const TexGSInputs* in, const TexGSGeom* g,
                        const TexGSBinning* b, const TexGSImage* img, TexGSGrads* gr, hipStream_t s) {
     const PixArgs a = make_pix(c, f, in, g, b, img);
     const TexBinArgs tb = make_bins(c, img, gr);
     const bool taps = in->texture != nullptr;
     const bool tex = taps && (gr->want & TEXGS_WANT_TEXTURE) && gr->dL_dtexture != nullptr;
     const bool geo = (gr->want & TEXGS_WANT_GAUSSIANS) != 0;
-    if (!tex && !geo) return;
+    if (!tex && !geo) return hipSuccess;
     if (tex && tb.rec)      // list offsets + cursors from the counts the forward left (one small workgroup)
         hipLaunchKernelGGL(k_bin_offsets, dim3(1), dim3(1024), 0, s, (int)tex_bin_count(c.R), (const uint32_t*)img->tex_bin_count,
                            gr->tex_bin_base, gr->tex_bin_cursor, gr->tex_bin_base + tex_bin_count(c.R) + 1, tb.stats);
@@ -889,16 +890,18 @@ void launch_render_bwd(const CamConst& c, const TexGSFrame* f, const TexGSInputs
     else if (tex)         K7_LAUNCH(k7_lds, true, false, false, true);
     else                  K7_LAUNCH(k7_occ, false, true, true, true);
 #undef K7_LAUNCH
+    return hipGetLastError();
 }
 
 bool tex_bins_enabled(const CamConst& c, const TexGSInputs* in, const TexGSImage* img, const TexGSGrads* gr) {
     return in->texture != nullptr && gr->dL_dtexture != nullptr && make_bins(c, img, gr).rec != nullptr;
 }
 
-void launch_texgrad_reduce(const CamConst& c, const TexGSImage* img, TexGSGrads* gr, hipStream_t s) {
+hipError_t launch_texgrad_reduce(const CamConst& c, const TexGSImage* img, TexGSGrads* gr, hipStream_t s) {
     const TexBinArgs tb = make_bins(c, img, gr);
-    if (!tb.rec) return;
+    if (!tb.rec) return hipSuccess;
     hipLaunchKernelGGL(k_texgrad_reduce, dim3((unsigned)tex_bin_count(c.R)), dim3(TB_THREADS), 0, s, c.R, tb, gr->dL_dtexture);
+    return hipGetLastError();
 }
 
 #ifdef K7_TRACE

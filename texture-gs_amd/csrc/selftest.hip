@@ -43,6 +43,7 @@ k_selftest_waveops(const float* __restrict__ seed, float* __restrict__ out) {
 
 }  // namespace
 
-void launch_selftest_waveops(const float* seed128, float* out576, hipStream_t s) {
+hipError_t launch_selftest_waveops(const float* seed128, float* out576, hipStream_t s) {
     hipLaunchKernelGGL(k_selftest_waveops, dim3(1), dim3(64), 0, s, seed128, out576);
+    return hipGetLastError();
 }

@@ -216,25 +216,25 @@ int hashgrid_levels(const TexGSHashGrid* g, float* scale, uint32_t* res, uint32_
     return 0;
 }
 
-int launch_hashgrid_forward(const TexGSHashGrid* g, const float* params, const float* x, int N, float* enc, hipStream_t s) {
+hipError_t launch_hashgrid_forward(const TexGSHashGrid* g, const float* params, const float* x, int N, float* enc, hipStream_t s) {
     HGDev d;
-    if (int r = hg_device_table(g, &d)) return r;
+    if (hg_device_table(g, &d)) return hipErrorInvalidValue;      // (abi.hip rejects such a grid first, with the reason)
     const uint64_t lanes = (uint64_t)N * d.L;
-    if (lanes == 0) return 0;
+    if (lanes == 0) return hipSuccess;
     hipLaunchKernelGGL(k_hg_forward, dim3((uint32_t)((lanes + HG_FWD_BLOCK - 1) / HG_FWD_BLOCK)), dim3(HG_FWD_BLOCK), 0, s, d, params, x,
                        (uint32_t)N, enc);
-    return 0;
+    return hipGetLastError();
 }
 
 size_t hashgrid_backward_temp_bytes(const TexGSHashGrid* g, int N) {
     return (size_t)g->n_levels * (size_t)(N > 0 ? N : 0) * 3 * sizeof(float);
 }
 
-int launch_hashgrid_backward(const TexGSHashGrid* g, const float* params, const float* x, const float* d_enc, int N, float* d_params,
+hipError_t launch_hashgrid_backward(const TexGSHashGrid* g, const float* params, const float* x, const float* d_enc, int N, float* d_params,
                              float* d_x, void* temp, hipStream_t s) {
     HGDev d;
-    if (int r = hg_device_table(g, &d)) return r;
-    if (N == 0 || (!d_params && !d_x)) return 0;
+    if (hg_device_table(g, &d)) return hipErrorInvalidValue;
+    if (N == 0 || (!d_params && !d_x)) return hipSuccess;
     float* dxl = d_x ? (float*)temp : nullptr;
     HGSel lds = {}, glob = {};
     uint32_t lds_max = 0;
@@ -263,17 +263,17 @@ int launch_hashgrid_backward(const TexGSHashGrid* g, const float* params, const 
     launch(glob, false);
     if (d_x)
         hipLaunchKernelGGL(k_hg_dx_reduce, dim3(((uint32_t)N * 3 + 255) / 256), dim3(256), 0, s, (const float*)dxl, d.L, (uint32_t)N, d_x);
-    return 0;
+    return hipGetLastError();
 }
 
 size_t chamfer_nn_temp_bytes(int P) { return (size_t)(P > 0 ? P : 0) * sizeof(unsigned long long); }
 
-int launch_chamfer_nn(const float* a, int P, const float* b, int Q, float* d2, int32_t* idx, void* temp, hipStream_t s) {
-    if (P == 0) return 0;
+hipError_t launch_chamfer_nn(const float* a, int P, const float* b, int Q, float* d2, int32_t* idx, void* temp, hipStream_t s) {
+    if (P == 0) return hipSuccess;
     unsigned long long* keys = (unsigned long long*)temp;
-    if (hipError_t e = hipMemsetAsync(keys, 0xff, (size_t)P * sizeof(unsigned long long), s)) return (int)e;
+    if (hipError_t e = hipMemsetAsync(keys, 0xff, (size_t)P * sizeof(unsigned long long), s)) return e;
     hipLaunchKernelGGL(k_nn_search, dim3(((uint32_t)P + NN_BLOCK - 1) / NN_BLOCK, ((uint32_t)Q + NN_SPLIT - 1) / NN_SPLIT), dim3(NN_BLOCK),
                        0, s, a, (uint32_t)P, b, (uint32_t)Q, keys);
     hipLaunchKernelGGL(k_nn_unpack, dim3(((uint32_t)P + 255) / 256), dim3(256), 0, s, (const unsigned long long*)keys, (uint32_t)P, d2, idx);
-    return 0;
+    return hipGetLastError();
 }

@@ -861,27 +861,25 @@ static UVArgs uv_args(const TexGSUVNet* net, int precision, const void* packed) 
             precision == TEXGS_UV_FP32 ? nullptr : reinterpret_cast<const uint4*>(p + uv_packed_b16_offset(precision))};
 }
 
-int launch_uv_pack(const TexGSUVNet* net, int precision, void* packed, hipStream_t s) {
+hipError_t launch_uv_pack(const TexGSUVNet* net, int precision, void* packed, hipStream_t s) {
     char* p = reinterpret_cast<char*>(packed);
-    if (precision != TEXGS_UV_BF16X3) {
+    if (precision != TEXGS_UV_BF16X3)
         hipLaunchKernelGGL(k_uv_pack, dim3(3 * 4 * 64 * 64 / 256), dim3(256), 0, s, net->W2, net->W3, net->W4, reinterpret_cast<float*>(p));
-        if (hipError_t e = hipGetLastError()) return (int)e;
-    }
     if (precision != TEXGS_UV_FP32)
         hipLaunchKernelGGL(k_uv_pack_bf16x3, dim3(3 * 4 * 8 * 64 / 256), dim3(256), 0, s, net->W2, net->W3, net->W4,
                            reinterpret_cast<uint4*>(p + uv_packed_b16_offset(precision)));
-    return (int)hipGetLastError();
+    return hipGetLastError();
 }
 
-int launch_uv_taylor_packed(const TexGSUVNet* net, int precision, const void* packed, const float* xyz, int N, float* uvs, float* grad_uvs,
+hipError_t launch_uv_taylor_packed(const TexGSUVNet* net, int precision, const void* packed, const float* xyz, int N, float* uvs, float* grad_uvs,
                             hipStream_t s) {
-    if (N <= 0) return 0;
+    if (N <= 0) return hipSuccess;
     const UVArgs a = uv_args(net, precision, packed);
     const dim3 grid((N + UV_P - 1) / UV_P), block(256);
     if (precision == TEXGS_UV_FP32) hipLaunchKernelGGL(k_uv_taylor, grid, block, 0, s, a, xyz, N, uvs, grad_uvs);
     else if (precision == TEXGS_UV_BF16X3) hipLaunchKernelGGL(k_uv_taylor_bf16x3, grid, block, 0, s, a, xyz, N, uvs, grad_uvs);
     else hipLaunchKernelGGL(k_uv_taylor_mixed, grid, block, 0, s, a, xyz, N, uvs, grad_uvs);
-    return (int)hipGetLastError();
+    return hipGetLastError();
 }
 
 // ---- backward: temp = [packed W2..W4][packed W2^T..W4^T][partials of `uv_backward_blocks(N)` workgroups]
@@ -891,7 +889,7 @@ size_t uv_backward_temp_bytes(int N) {
     return 2 * UV_PACK_BYTES + (size_t)uv_backward_blocks(N) * uv_backward_part_floats() * sizeof(float);
 }
 
-int launch_uv_backward(const TexGSUVNet* net, const float* xyz, const float* g, int N, const TexGSUVNetGrad* out, void* temp, int mixed,
+hipError_t launch_uv_backward(const TexGSUVNet* net, const float* xyz, const float* g, int N, const TexGSUVNetGrad* out, void* temp, int mixed,
                        hipStream_t s) {
     const int G = uv_backward_blocks(N);
     float* packed = reinterpret_cast<float*>(temp);
@@ -899,8 +897,9 @@ int launch_uv_backward(const TexGSUVNet* net, const float* xyz, const float* g, 
     float* partS = partW + (size_t)G * 3 * UV_H * UV_H;
     float* partB5 = partS + (size_t)G * 2 * BW_SMALL * UV_H;
     UVGradOut o{out->dW1, out->db1, out->dW2, out->db2, out->dW3, out->db3, out->dW4, out->db4, out->dW5, out->db5};
+    LaunchStatus st;
     if (N <= 0) {                                          // no points: every gradient is zero
-        (void)hipMemsetAsync(partW, 0, (size_t)G * uv_backward_part_floats() * sizeof(float), s);
+        st += hipMemsetAsync(partW, 0, (size_t)G * uv_backward_part_floats() * sizeof(float), s);
     } else {
         if (mixed) {        // W2..W4 in f32 A-operand order (forward recomputation), W2^T..W4^T as split bf16
             hipLaunchKernelGGL(k_uv_pack_bwd, dim3(3 * 4 * 64 * 64 / 256), dim3(256), 0, s, net->W2, net->W3, net->W4, packed, 3);
@@ -915,5 +914,5 @@ int launch_uv_backward(const TexGSUVNet* net, const float* xyz, const float* g, 
     }
     const int n_out = 3 * UV_H * UV_H + BW_SMALL * UV_H + 3;
     hipLaunchKernelGGL(k_uv_backward_reduce, dim3((n_out + 255) / 256), dim3(256), 0, s, partW, partS, partB5, G, o);
-    return (int)hipGetLastError();
+    return st.after_launches();
 }

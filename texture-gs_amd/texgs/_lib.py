@@ -1,5 +1,6 @@
 """ctypes binding of libtexgs.so (C ABI in include/texgs.h).  Fails loudly when the HIP library is missing:
 there is no CPU / eager fallback for the product path."""
+import contextlib
 import ctypes as C
 import os
 
@@ -98,18 +99,63 @@ class DensityMoveStruct(C.Structure):
 UV_PRECISION = {"fp32": 0, "bf16x3": 1, "mixed": 2}          # TEXGS_UV_FP32 / _BF16X3 / _MIXED
 
 
-EXPORTS = ["texgs_abi_version", "texgs_build_id", "texgs_last_error", "texgs_scan_temp_bytes", "texgs_sort_temp_bytes",
-           "texgs_preprocess_forward", "texgs_num_rendered_words", "texgs_num_rendered_begin", "texgs_num_rendered_reduce", "texgs_depth_sort_scan", "texgs_bin_sort_render_forward",
-           "texgs_render_forward", "texgs_backward", "texgs_backward_render", "texgs_backward_preprocess",
-           "texgs_rgb_alpha_loss", "texgs_mark_visible", "texgs_profile_enable", "texgs_tex_bin_count",
-           "texgs_profile_read", "texgs_profile_select", "texgs_selftest_waveops", "texgs_geom_losses", "texgs_norm_from_depth",
-           "texgs_uv_packed_bytes", "texgs_uv_pack", "texgs_uv_taylor_packed", "texgs_uv_backward", "texgs_uv_backward_temp_bytes",
-           "texgs_hashgrid_levels", "texgs_hashgrid_forward", "texgs_hashgrid_backward_temp_bytes", "texgs_hashgrid_backward",
-           "texgs_chamfer_nn_temp_bytes", "texgs_chamfer_nn",
-           "texgs_knn3_temp_bytes", "texgs_knn3_mean_dist2", "texgs_fps_temp_bytes", "texgs_farthest_points",
-           "texgs_cube_sample", "texgs_cube_latlong", "texgs_cube_sample_backward", "texgs_cube_sample_nearest_backward",
-           "texgs_density_stats", "texgs_density_plan_temp_bytes", "texgs_density_plan", "texgs_density_move",
-           "texgs_eval_metrics_temp_bytes", "texgs_eval_metrics"]
+_P = C.POINTER
+_i32, _u32, _f32, _size, _vp = C.c_int32, C.c_uint32, C.c_float, C.c_size_t, C.c_void_p
+_frame5 = [_P(Frame), _P(Inputs), _P(Geom), _P(Binning), _P(Image)]
+# The C ABI, stated once: name -> (restype, argtypes), in the order of include/texgs.h (tests/test_abi.py compares every entry with the
+# header's prototype).  load() applies it; EXPORTS is its key list.
+SIGNATURES = {
+    "texgs_abi_version": (C.c_int, []),
+    "texgs_build_id": (C.c_char_p, []),
+    "texgs_last_error": (C.c_char_p, []),
+    "texgs_scan_temp_bytes": (_size, [_i32]),
+    "texgs_sort_temp_bytes": (_size, [_u32, _u32]),
+    "texgs_tex_bin_count": (_size, [_i32]),
+    "texgs_preprocess_forward": (C.c_int, [_P(Frame), _P(Inputs), _P(Geom), _vp]),
+    "texgs_num_rendered_words": (_size, [_i32]),
+    "texgs_num_rendered_begin": (C.c_int, [_P(Geom), _i32, _vp, _size, _i32, _vp]),
+    "texgs_num_rendered_reduce": (C.c_int, [_vp, _i32, _P(_u32), _P(C.c_uint64)]),
+    "texgs_depth_sort_scan": (C.c_int, [_P(Geom), _i32, _vp]),
+    "texgs_bin_sort_render_forward": (C.c_int, _frame5 + [_vp]),
+    "texgs_render_forward": (C.c_int, _frame5 + [_vp]),
+    "texgs_backward": (C.c_int, _frame5 + [_P(Grads), _vp]),
+    "texgs_backward_render": (C.c_int, _frame5 + [_P(Grads), _vp]),
+    "texgs_backward_preprocess": (C.c_int, [_P(Frame), _P(Inputs), _P(Geom), _P(Grads), _vp]),
+    "texgs_profile_enable": (C.c_int, [C.c_int]),
+    "texgs_profile_select": (C.c_int, [_u32]),
+    "texgs_profile_read": (C.c_int, [_P(_f32), _P(_u32)]),
+    "texgs_rgb_alpha_loss": (C.c_int, [_vp] * 4 + [_i32, _i32, _f32, _f32] + [_vp] * 5),
+    "texgs_geom_losses": (C.c_int, [_vp] * 6 + [_i32, _i32, _f32, _f32, _f32, _f32] + [_vp] * 4),
+    "texgs_norm_from_depth": (C.c_int, [_vp, _vp, _f32, _f32, _i32, _i32, _f32, _vp, _vp, _vp]),
+    "texgs_uv_packed_bytes": (_size, [_i32]),
+    "texgs_uv_pack": (C.c_int, [_P(UVNetStruct), _i32, _vp, _vp]),
+    "texgs_uv_taylor_packed": (C.c_int, [_P(UVNetStruct), _i32, _vp, _vp, _i32, _vp, _vp, _vp]),
+    "texgs_uv_backward_temp_bytes": (_size, [_i32]),
+    "texgs_uv_backward": (C.c_int, [_P(UVNetStruct), _i32, _vp, _vp, _i32, _P(UVNetGradStruct), _vp, _vp]),
+    "texgs_hashgrid_levels": (C.c_int, [_P(HashGridStruct), _vp, _vp, _vp, _vp, _P(_u32)]),
+    "texgs_hashgrid_forward": (C.c_int, [_P(HashGridStruct), _vp, _vp, _i32, _vp, _vp]),
+    "texgs_hashgrid_backward_temp_bytes": (_size, [_P(HashGridStruct), _i32]),
+    "texgs_hashgrid_backward": (C.c_int, [_P(HashGridStruct), _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "texgs_chamfer_nn_temp_bytes": (_size, [_i32]),
+    "texgs_chamfer_nn": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "texgs_knn3_temp_bytes": (_size, [_i32]),
+    "texgs_knn3_mean_dist2": (C.c_int, [_vp, _i32, _vp, _vp, _vp]),
+    "texgs_fps_temp_bytes": (_size, [_i32, _i32]),
+    "texgs_farthest_points": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "texgs_cube_sample": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, _i32, _vp, _vp]),
+    "texgs_cube_latlong": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "texgs_cube_sample_backward": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "texgs_cube_sample_nearest_backward": (C.c_int, [_i32, _i32, _vp, _i32, _vp, _vp, _vp]),
+    "texgs_density_stats": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "texgs_density_plan_temp_bytes": (_size, [_i32]),
+    "texgs_density_plan": (C.c_int, [_P(DensityPlanStruct), _vp, _vp, _vp, _vp, _vp]),
+    "texgs_density_move": (C.c_int, [_P(DensityMoveStruct), _vp]),
+    "texgs_eval_metrics_temp_bytes": (_size, [_i32, _i32]),
+    "texgs_eval_metrics": (C.c_int, [_vp] * 5 + [_i32, _i32, _i32, _vp, _vp, _vp]),
+    "texgs_selftest_waveops": (C.c_int, [_vp, _vp, _vp]),
+    "texgs_mark_visible": (C.c_int, [_P(Frame), _vp, _vp, _vp]),
+}
+EXPORTS = list(SIGNATURES)
 KERNEL_NAMES = ["preprocess_fwd", "scan", "duplicate", "sort", "ranges", "render_fwd", "render_bwd", "preprocess_bwd",
                 "texgrad_reduce"]
 
@@ -130,109 +176,14 @@ def load():
     if missing:         # a library from before an additive change of the ABI (the version number stays): same advice as a stale version
         raise RuntimeError(f"libtexgs.so at {LIB_PATH} does not export {', '.join(missing)}; rebuild it with "
                            "`python texture-gs_amd/build.py`")
-    P = C.POINTER
-    lib.texgs_abi_version.restype = C.c_int
-    lib.texgs_last_error.restype = C.c_char_p
-    lib.texgs_scan_temp_bytes.restype = C.c_size_t
-    lib.texgs_scan_temp_bytes.argtypes = [C.c_int32]
-    lib.texgs_sort_temp_bytes.restype = C.c_size_t
-    lib.texgs_sort_temp_bytes.argtypes = [C.c_uint32, C.c_uint32]
-    lib.texgs_tex_bin_count.restype = C.c_size_t
-    lib.texgs_tex_bin_count.argtypes = [C.c_int32]
-    lib.texgs_preprocess_forward.argtypes = [P(Frame), P(Inputs), P(Geom), C.c_void_p]
-    lib.texgs_num_rendered_words.argtypes = [C.c_int32]
-    lib.texgs_num_rendered_words.restype = C.c_size_t
-    lib.texgs_num_rendered_begin.argtypes = [P(Geom), C.c_int32, C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p]
-    lib.texgs_num_rendered_begin.restype = C.c_int
-    lib.texgs_num_rendered_reduce.argtypes = [C.c_void_p, C.c_int32, P(C.c_uint32), P(C.c_uint64)]
-    lib.texgs_num_rendered_reduce.restype = C.c_int
-    lib.texgs_depth_sort_scan.argtypes = [P(Geom), C.c_int32, C.c_void_p]
-    lib.texgs_depth_sort_scan.restype = C.c_int
-    lib.texgs_bin_sort_render_forward.argtypes = [P(Frame), P(Inputs), P(Geom), P(Binning), P(Image), C.c_void_p]
-    lib.texgs_render_forward.argtypes = [P(Frame), P(Inputs), P(Geom), P(Binning), P(Image), C.c_void_p]
-    lib.texgs_backward.argtypes = [P(Frame), P(Inputs), P(Geom), P(Binning), P(Image), P(Grads), C.c_void_p]
-    lib.texgs_backward_render.argtypes = [P(Frame), P(Inputs), P(Geom), P(Binning), P(Image), P(Grads), C.c_void_p]
-    lib.texgs_backward_preprocess.argtypes = [P(Frame), P(Inputs), P(Geom), P(Grads), C.c_void_p]
-    lib.texgs_mark_visible.argtypes = [P(Frame), C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.texgs_rgb_alpha_loss.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float,
-                                         C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.texgs_rgb_alpha_loss.restype = C.c_int
-    lib.texgs_geom_losses.argtypes = [C.c_void_p] * 6 + [C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float,
-                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.texgs_geom_losses.restype = C.c_int
-    lib.texgs_norm_from_depth.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_int32, C.c_int32, C.c_float,
-                                          C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.texgs_norm_from_depth.restype = C.c_int
-    lib.texgs_uv_packed_bytes.argtypes = [C.c_int32]
-    lib.texgs_uv_packed_bytes.restype = C.c_size_t
-    lib.texgs_uv_pack.argtypes = [P(UVNetStruct), C.c_int32, C.c_void_p, C.c_void_p]
-    lib.texgs_uv_pack.restype = C.c_int
-    lib.texgs_uv_taylor_packed.argtypes = [P(UVNetStruct), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.texgs_uv_taylor_packed.restype = C.c_int
-    lib.texgs_uv_backward_temp_bytes.argtypes = [C.c_int32]
-    lib.texgs_uv_backward_temp_bytes.restype = C.c_size_t
-    lib.texgs_uv_backward.argtypes = [P(UVNetStruct), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, P(UVNetGradStruct), C.c_void_p, C.c_void_p]
-    lib.texgs_uv_backward.restype = C.c_int
-    lib.texgs_hashgrid_levels.argtypes = [P(HashGridStruct), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, P(C.c_uint32)]
-    lib.texgs_hashgrid_levels.restype = C.c_int
-    lib.texgs_hashgrid_forward.argtypes = [P(HashGridStruct), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
-    lib.texgs_hashgrid_forward.restype = C.c_int
-    lib.texgs_hashgrid_backward_temp_bytes.argtypes = [P(HashGridStruct), C.c_int32]
-    lib.texgs_hashgrid_backward_temp_bytes.restype = C.c_size_t
-    lib.texgs_hashgrid_backward.argtypes = [P(HashGridStruct), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
-                                            C.c_void_p, C.c_void_p]
-    lib.texgs_hashgrid_backward.restype = C.c_int
-    lib.texgs_chamfer_nn_temp_bytes.argtypes = [C.c_int32]
-    lib.texgs_chamfer_nn_temp_bytes.restype = C.c_size_t
-    lib.texgs_chamfer_nn.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.texgs_chamfer_nn.restype = C.c_int
-    lib.texgs_knn3_temp_bytes.argtypes = [C.c_int32]
-    lib.texgs_knn3_temp_bytes.restype = C.c_size_t
-    lib.texgs_knn3_mean_dist2.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.texgs_knn3_mean_dist2.restype = C.c_int
-    lib.texgs_fps_temp_bytes.argtypes = [C.c_int32, C.c_int32]
-    lib.texgs_fps_temp_bytes.restype = C.c_size_t
-    lib.texgs_farthest_points.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.texgs_farthest_points.restype = C.c_int
-    lib.texgs_cube_sample.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
-    lib.texgs_cube_sample.restype = C.c_int
-    lib.texgs_cube_latlong.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
-    lib.texgs_cube_latlong.restype = C.c_int
-    lib.texgs_cube_sample_backward.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
-                                               C.c_void_p]
-    lib.texgs_cube_sample_backward.restype = C.c_int
-    lib.texgs_cube_sample_nearest_backward.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.texgs_cube_sample_nearest_backward.restype = C.c_int
-    lib.texgs_density_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.texgs_density_stats.restype = C.c_int
-    lib.texgs_density_plan_temp_bytes.argtypes = [C.c_int32]
-    lib.texgs_density_plan_temp_bytes.restype = C.c_size_t
-    lib.texgs_density_plan.argtypes = [P(DensityPlanStruct), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.texgs_density_plan.restype = C.c_int
-    lib.texgs_density_move.argtypes = [P(DensityMoveStruct), C.c_void_p]
-    lib.texgs_density_move.restype = C.c_int
-    lib.texgs_eval_metrics_temp_bytes.argtypes = [C.c_int32, C.c_int32]
-    lib.texgs_eval_metrics_temp_bytes.restype = C.c_size_t
-    lib.texgs_eval_metrics.argtypes = [C.c_void_p] * 5 + [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.texgs_eval_metrics.restype = C.c_int
-    lib.texgs_selftest_waveops.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.texgs_selftest_waveops.restype = C.c_int
-    lib.texgs_profile_enable.argtypes = [C.c_int]
-    lib.texgs_profile_enable.restype = C.c_int
-    lib.texgs_profile_select.argtypes = [C.c_uint32]
-    lib.texgs_profile_select.restype = C.c_int
-    lib.texgs_profile_read.argtypes = [P(C.c_float), P(C.c_uint32)]
-    lib.texgs_profile_read.restype = C.c_int
-    for name in ("texgs_preprocess_forward", "texgs_bin_sort_render_forward",
-                 "texgs_render_forward", "texgs_backward", "texgs_backward_render",
-                 "texgs_backward_preprocess", "texgs_rgb_alpha_loss", "texgs_mark_visible"):
-        getattr(lib, name).restype = C.c_int
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
     v = lib.texgs_abi_version()
     if v != ABI_VERSION:
         # (no bypass in the shipped loader -- the struct layouts differ between versions; experiment scripts that A/B an
         #  older build must run it under that build's own host layer)
         raise RuntimeError(f"libtexgs.so ABI version {v} != expected {ABI_VERSION}; rebuild it")
-    lib.texgs_build_id.restype = C.c_char_p
     global BUILD_ID
     BUILD_ID = lib.texgs_build_id().decode()
     if not os.environ.get("TEXGS_LIB"):          # the product library must be built from THIS tree's sources (experiment builds: any)
@@ -265,12 +216,32 @@ def check(rc, what):
         raise RuntimeError(f"{what} failed (code {rc}): {msg}")
 
 
+def call(fn, *args):
+    """Run one int-returning entry point of the library (`call(lib.texgs_x, ...)`); a non-zero code raises with the function's name."""
+    rc = fn(*args)
+    if rc != 0:         # (tested here, not only in check: the per-view path makes a dozen of these calls)
+        check(rc, fn.__name__)
+
+
+def ptr(t):
+    """Device pointer of an optional tensor (None travels as NULL)."""
+    return None if t is None else t.data_ptr()
+
+
+@contextlib.contextmanager
+def on(device):
+    """Make `device` current and yield the raw handle of its current stream (the last argument of every launching entry point)."""
+    import torch
+    with torch.cuda.device(device):
+        yield torch.cuda.current_stream(device).cuda_stream
+
+
 def profile_enable(on: bool, only=None):
     """Bracket kernel launches with HIP events.  `only`: iterable of KERNEL_NAMES to restrict to (an event pair costs a few
     microseconds of stream time, so a timed region should bracket as little as it needs)."""
     mask = 0xFFFFFFFF if only is None else sum(1 << KERNEL_NAMES.index(n) for n in only)
-    check(load().texgs_profile_select(mask), "texgs_profile_select")
-    check(load().texgs_profile_enable(1 if on else 0), "texgs_profile_enable")
+    call(load().texgs_profile_select, mask)
+    call(load().texgs_profile_enable, 1 if on else 0)
 
 
 def profile_read():
@@ -278,5 +249,5 @@ def profile_read():
     n = len(KERNEL_NAMES)
     ms = (C.c_float * n)()
     cnt = (C.c_uint32 * n)()
-    check(load().texgs_profile_read(ms, cnt), "texgs_profile_read")
+    call(load().texgs_profile_read, ms, cnt)
     return {KERNEL_NAMES[i]: (float(ms[i]), int(cnt[i])) for i in range(n)}

@@ -92,10 +92,8 @@ def _forward(texture, dirs, filter, tap_map):
     R, C = texture.shape[1], texture.shape[3]
     n = dirs.shape[0]
     out = torch.empty(n, C, dtype=torch.float32, device=texture.device)
-    with torch.cuda.device(texture.device):
-        stream = torch.cuda.current_stream(texture.device).cuda_stream
-        _lib.check(lib.texgs_cube_sample(texture.data_ptr(), R, C, dirs.data_ptr(), n, FILTERS[filter], int(tap_map), out.data_ptr(),
-                                         stream), "texgs_cube_sample")
+    with _lib.on(texture.device) as stream:
+        _lib.call(lib.texgs_cube_sample, texture.data_ptr(), R, C, dirs.data_ptr(), n, FILTERS[filter], int(tap_map), out.data_ptr(), stream)
     return out
 
 
@@ -123,16 +121,12 @@ class _CubeSample(torch.autograd.Function):
         d_dirs = torch.empty_like(d) if want_dirs else None
         if want_tex or want_dirs:
             lib = _lib.load()
-            with torch.cuda.device(tex.device):
-                stream = torch.cuda.current_stream(tex.device).cuda_stream
+            with _lib.on(tex.device) as stream:
                 if ctx.filter == "linear":
-                    _lib.check(lib.texgs_cube_sample_backward(tex.data_ptr(), R, C, d.data_ptr(), n, g.data_ptr(),
-                                                              d_tex.data_ptr() if want_tex else None,
-                                                              d_dirs.data_ptr() if want_dirs else None, stream),
-                               "texgs_cube_sample_backward")
+                    _lib.call(lib.texgs_cube_sample_backward, tex.data_ptr(), R, C, d.data_ptr(), n, g.data_ptr(), _lib.ptr(d_tex),
+                              _lib.ptr(d_dirs), stream)
                 else:
-                    _lib.check(lib.texgs_cube_sample_nearest_backward(R, C, d.data_ptr(), n, g.data_ptr(), d_tex.data_ptr(), stream),
-                               "texgs_cube_sample_nearest_backward")
+                    _lib.call(lib.texgs_cube_sample_nearest_backward, R, C, d.data_ptr(), n, g.data_ptr(), d_tex.data_ptr(), stream)
         return d_tex, (d_dirs.reshape(ctx.dirs_shape) if want_dirs else None), None
 
 
@@ -167,9 +161,8 @@ def _latlong(texture, resolution, tap_map, what):
     tex = texture.detach().contiguous()
     R, C = tex.shape[1], tex.shape[3]
     out = torch.empty(h, w, C, dtype=torch.float32, device=tex.device)
-    with torch.cuda.device(tex.device):
-        stream = torch.cuda.current_stream(tex.device).cuda_stream
-        _lib.check(lib.texgs_cube_latlong(tex.data_ptr(), R, C, h, w, int(tap_map), out.data_ptr(), stream), "texgs_cube_latlong")
+    with _lib.on(tex.device) as stream:
+        _lib.call(lib.texgs_cube_latlong, tex.data_ptr(), R, C, h, w, int(tap_map), out.data_ptr(), stream)
     return out
 
 

@@ -107,10 +107,9 @@ def add_densification_stats(state, viewspace_grad, radii):
     _on_gpu(seen)
     dev = state.max_radii2D.device
     lib = _lib.load()
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        _lib.check(lib.texgs_density_stats(viewspace_grad.data_ptr(), radii.data_ptr(), n, state.xyz_gradient_accum.data_ptr(),
-                                           state.denom.data_ptr(), state.max_radii2D.data_ptr(), stream), "texgs_density_stats")
+    with _lib.on(dev) as stream:
+        _lib.call(lib.texgs_density_stats, viewspace_grad.data_ptr(), radii.data_ptr(), n, state.xyz_gradient_accum.data_ptr(),
+                  state.denom.data_ptr(), state.max_radii2D.data_ptr(), stream)
 
 
 def _groups(params, optimizer, what, seen):
@@ -173,8 +172,7 @@ def _plan(lib, data, state, n, dev, stream, max_grad, min_opacity, dense_scale, 
     plan = _lib.DensityPlanStruct(state.xyz_gradient_accum.data_ptr() if densify else None, state.denom.data_ptr() if densify else None,
                                   data["scaling"].data_ptr(), data["opacity"].data_ptr(), n, max_grad, min_opacity, dense_scale,
                                   big_scale, int(densify), int(use_big))
-    _lib.check(lib.texgs_density_plan(C.byref(plan), action.data_ptr(), rank.data_ptr(), totals.data_ptr(), temp.data_ptr(), stream),
-               "texgs_density_plan")
+    _lib.call(lib.texgs_density_plan, C.byref(plan), action.data_ptr(), rank.data_ptr(), totals.data_ptr(), temp.data_ptr(), stream)
     return action, rank, totals
 
 
@@ -199,8 +197,7 @@ def _plan_densify(params_data, state, *, max_grad, min_opacity, dense_scale, big
     _on_gpu(seen)
     dev = state.max_radii2D.device
     lib = _lib.load()
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
+    with _lib.on(dev) as stream:
         action, rank, totals = _plan(lib, params_data, state, n, dev, stream, max_grad, min_opacity, dense_scale, big_scale, bool(densify),
                                      bool(use_big))
     return action[:n], rank[:, :n], totals
@@ -216,8 +213,7 @@ def _resize(what, params, optimizer, state, max_grad, min_opacity, dense_scale, 
     _on_gpu(seen)
     dev = data["xyz"].device
     lib = _lib.load()
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
+    with _lib.on(dev) as stream:
         action, rank, totals = _plan(lib, data, state, n, dev, stream, max_grad, min_opacity, dense_scale, big_scale, densify, use_big)
         n_kept, n_clone, n_split, n_child = (int(v) for v in totals.tolist())        # the call's one synchronisation
         m = n_kept + n_clone + 2 * n_child
@@ -257,7 +253,7 @@ def _resize(what, params, optimizer, state, max_grad, min_opacity, dense_scale, 
         move.n_kept, move.n_clone, move.n_split, move.n_child = n_kept, n_clone, n_split, n_child
         move.scaling, move.rotation = data["scaling"].data_ptr(), data["rotation"].data_ptr()
         move.noise = noise.data_ptr() if n_split else None
-        _lib.check(lib.texgs_density_move(C.byref(move), stream), "texgs_density_move")
+        _lib.call(lib.texgs_density_move, C.byref(move), stream)
     out = {}
     for name in GROUPS:         # the optimizer's state, edited as _prune_optimizer / cat_tensors_to_optimizer edit it (:200-254)
         group = by_name[name]

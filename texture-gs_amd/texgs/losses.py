@@ -2,8 +2,6 @@
 TextureGaussian3D.compute_loss (models/texture_gaussian3d.py:333-345), as two HBM-bound HIP kernels instead of the
 reference's 5 depthwise conv2d + ~25 elementwise kernels and their autograd.  The gradient w.r.t. the rendered image /
 alpha is computed in the same pass and handed to autograd, i.e. straight to the rasterizer's backward."""
-import ctypes as C
-
 import torch
 
 from . import _lib
@@ -48,11 +46,10 @@ class _RgbAlphaLoss(torch.autograd.Function):
         sums = torch.empty(4, dtype=torch.float32, device=dev)
         d_img = torch.empty_like(img)
         d_a = torch.empty_like(a) if use_alpha else None
-        p = lambda t: None if t is None else t.data_ptr()
-        with torch.cuda.device(dev):
-            _lib.check(lib.texgs_rgb_alpha_loss(p(img), p(gt), p(a), p(ga), H, W, float(lambda_dssim), float(lambda_alpha),
-                                                p(scratch), p(sums), p(d_img), p(d_a),
-                                                torch.cuda.current_stream(dev).cuda_stream), "texgs_rgb_alpha_loss")
+        p = _lib.ptr
+        with _lib.on(dev) as stream:
+            _lib.call(lib.texgs_rgb_alpha_loss, p(img), p(gt), p(a), p(ga), H, W, float(lambda_dssim), float(lambda_alpha),
+                      p(scratch), p(sums), p(d_img), p(d_a), stream)
         n = 3.0 * H * W
         l1 = sums[0] / n
         ssim = sums[1] / n
@@ -117,11 +114,10 @@ class _GeomLosses(torch.autograd.Function):
         sums = torch.empty(12, dtype=torch.float32, device=dev)
         d_n = torch.empty_like(n) if use_n else None
         d_d = torch.empty_like(d) if use_d else None
-        p = lambda t: None if t is None else t.data_ptr()
-        with torch.cuda.device(dev):
-            _lib.check(lib.texgs_geom_losses(p(n), p(gn), p(gi), p(m), p(d), p(gd), H, W, float(lambda_norm), float(lambda_smooth),
-                                             float(gamma), float(lambda_depth), p(sums), p(d_n), p(d_d),
-                                             torch.cuda.current_stream(dev).cuda_stream), "texgs_geom_losses")
+        p = _lib.ptr
+        with _lib.on(dev) as stream:
+            _lib.call(lib.texgs_geom_losses, p(n), p(gn), p(gi), p(m), p(d), p(gd), H, W, float(lambda_norm), float(lambda_smooth),
+                      float(gamma), float(lambda_depth), p(sums), p(d_n), p(d_d), stream)
         loss = sums.new_zeros(())
         stats = {}
         if lambda_norm != 0.0:
@@ -174,10 +170,9 @@ def norm_from_depth(depth, world_view_transform, tanfovx, tanfovy, threshold=1e-
         raise ValueError("world_view_transform must be [4,4]")
     norm = torch.empty(3, H, W, dtype=torch.float32, device=depth.device)
     mask = torch.empty(1, H, W, dtype=torch.float32, device=depth.device)
-    with torch.cuda.device(depth.device):
-        _lib.check(lib.texgs_norm_from_depth(depth.data_ptr(), vm.data_ptr(), float(tanfovx), float(tanfovy), H, W, float(threshold),
-                                             norm.data_ptr(), mask.data_ptr(),
-                                             torch.cuda.current_stream(depth.device).cuda_stream), "texgs_norm_from_depth")
+    with _lib.on(depth.device) as stream:
+        _lib.call(lib.texgs_norm_from_depth, depth.data_ptr(), vm.data_ptr(), float(tanfovx), float(tanfovy), H, W, float(threshold),
+                  norm.data_ptr(), mask.data_ptr(), stream)
     return norm, mask
 
 

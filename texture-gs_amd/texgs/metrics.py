@@ -65,11 +65,10 @@ def _launch(image, gt_image, norm, gt_norm, alpha, H, W, clamp, table, v):
     lib = _lib.load()
     dev = image.device
     temp = torch.empty(lib.texgs_eval_metrics_temp_bytes(H, W) // 8, dtype=torch.float64, device=dev)
-    p = lambda t: None if t is None else t.data_ptr()
-    with torch.cuda.device(dev):
-        _lib.check(lib.texgs_eval_metrics(p(image), p(gt_image), p(norm), p(gt_norm), p(alpha), H, W, 1 if clamp else 0, p(temp),
-                                          table.data_ptr() + v * ROW * 8, torch.cuda.current_stream(dev).cuda_stream),
-                   "texgs_eval_metrics")
+    p = _lib.ptr
+    with _lib.on(dev) as stream:
+        _lib.call(lib.texgs_eval_metrics, p(image), p(gt_image), p(norm), p(gt_norm), p(alpha), H, W, 1 if clamp else 0, p(temp),
+                  table.data_ptr() + v * ROW * 8, stream)
 
 
 def _det(*ts):

@@ -44,10 +44,9 @@ def knn3_mean_dist2(points):
     lib = _lib.load()
     n = p.shape[0]
     out = torch.empty(n, dtype=torch.float32, device=p.device)
-    with torch.cuda.device(p.device):
-        stream = torch.cuda.current_stream(p.device).cuda_stream
+    with _lib.on(p.device) as stream:
         temp = torch.empty(lib.texgs_knn3_temp_bytes(n), dtype=torch.uint8, device=p.device)
-        _lib.check(lib.texgs_knn3_mean_dist2(p.data_ptr(), n, out.data_ptr(), temp.data_ptr(), stream), "texgs_knn3_mean_dist2")
+        _lib.call(lib.texgs_knn3_mean_dist2, p.data_ptr(), n, out.data_ptr(), temp.data_ptr(), stream)
     return out
 
 
@@ -71,11 +70,9 @@ def sample_farthest_points(points, K, start_index=0):
     lib = _lib.load()
     n = p.shape[0]
     idx = torch.empty(K, dtype=torch.int32, device=p.device)
-    with torch.cuda.device(p.device):
-        stream = torch.cuda.current_stream(p.device).cuda_stream
+    with _lib.on(p.device) as stream:
         temp = torch.empty(lib.texgs_fps_temp_bytes(n, K), dtype=torch.uint8, device=p.device)
-        _lib.check(lib.texgs_farthest_points(p.data_ptr(), n, K, start_index, idx.data_ptr(), temp.data_ptr(), stream),
-                   "texgs_farthest_points")
+        _lib.call(lib.texgs_farthest_points, p.data_ptr(), n, K, start_index, idx.data_ptr(), temp.data_ptr(), stream)
     idx = idx.long()
     return points[idx], idx
 

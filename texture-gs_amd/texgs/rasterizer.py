@@ -11,7 +11,7 @@ import os as _os
 import threading as _threading
 from collections import namedtuple
 from types import SimpleNamespace
-from typing import NamedTuple, Optional
+from typing import NamedTuple
 
 import torch
 from torch import nn
@@ -47,8 +47,7 @@ class GaussianRasterizationSettings(NamedTuple):
     debug: bool
 
 
-def _ptr(t: Optional[torch.Tensor]):
-    return None if t is None else t.data_ptr()
+_ptr = _lib.ptr         # bound once: a view's forward and backward take about forty pointers
 
 
 def _f32c(t: torch.Tensor, name: str, device) -> torch.Tensor:
@@ -450,14 +449,14 @@ class _Forward:
             if entry is None:
                 self._alloc_bin(self.cap, fix)
             refs = self.refs = [C.byref(x) for x in (self.frame, self.inputs, self.geom)]
-            _lib.check(lib.texgs_preprocess_forward(*refs, stream), "texgs_preprocess_forward")
+            _lib.call(lib.texgs_preprocess_forward, *refs, stream)
             # the one device->host read of a forward, in two steps: the copy into pinned memory is issued here, finish() waits for it
             pin = self.pin = _pin_take(int(lib.texgs_num_rendered_words(N)))
-            _lib.check(lib.texgs_num_rendered_begin(refs[2], N, pin.data_ptr(), pin.numel(), 0, stream), "texgs_num_rendered_begin")
+            _lib.call(lib.texgs_num_rendered_begin, refs[2], N, pin.data_ptr(), pin.numel(), 0, stream)
             self.d_ev = torch.cuda.Event()
             self.d_ev.record(cur_stream)
             if entry is None:           # K2 behind the event: the host waits for K1 + the copy only, the device goes on sorting
-                _lib.check(lib.texgs_depth_sort_scan(refs[2], N, stream), "texgs_depth_sort_scan")
+                _lib.call(lib.texgs_depth_sort_scan, refs[2], N, stream)
         return self
 
     def _add_lists(self, ar):           # per-tile pieces of the lists (a candidate adds them only if it has to build lists after all)
@@ -493,7 +492,7 @@ class _Forward:
         with torch.cuda.device(a.means3D.device):
             self.d_ev.synchronize()
             d_host, fp_host = C.c_uint32(0), C.c_uint64(0)
-            _lib.check(lib.texgs_num_rendered_reduce(pin.data_ptr(), a.N, C.byref(d_host), C.byref(fp_host)), "texgs_num_rendered_reduce")
+            _lib.call(lib.texgs_num_rendered_reduce, pin.data_ptr(), a.N, C.byref(d_host), C.byref(fp_host))
             _pin_give(pin)
             D, fp = int(d_host.value), int(fp_host.value)
             shared = entry is not None and fp == entry.fingerprint and D == entry.D
@@ -501,7 +500,7 @@ class _Forward:
                 # same geometry as the forward that built `entry`: its lists are this forward's lists; K6 alone, no hand-off work
                 _GEOM_STATS["hits"] += 1
                 binning, cap = _lib.Binning(D, *entry.bin), entry.cap
-                _lib.check(lib.texgs_render_forward(*refs, C.byref(binning), C.byref(img), stream), "texgs_render_forward")
+                _lib.call(lib.texgs_render_forward, *refs, C.byref(binning), C.byref(img), stream)
                 if for_backward and entry.handoff and (entry.counts or not self.want_counts):
                     img.survivors, img.surv_qmask, img.surv_count = entry.handoff
                     img.tex_bin_count, img.tex_bin_resv = entry.counts if self.want_counts else (None, None)
@@ -511,13 +510,13 @@ class _Forward:
                 if entry is not None:       # expected to share, cannot: build the lists after all (K2 was not started before the sync)
                     cap = max(cap, grown)
                     self._alloc_bin(cap, None)
-                    _lib.check(lib.texgs_depth_sort_scan(refs[2], a.N, stream), "texgs_depth_sort_scan")
+                    _lib.call(lib.texgs_depth_sort_scan, refs[2], a.N, stream)
                 elif D > cap:               # rare: grow
                     cap = grown
                     self._alloc_bin(cap, self.fix)
                 binning = self.binning
                 binning.num_rendered = D
-                _lib.check(lib.texgs_bin_sort_render_forward(*refs, C.byref(binning), C.byref(img), stream), "texgs_bin_sort_render_forward")
+                _lib.call(lib.texgs_bin_sort_render_forward, *refs, C.byref(binning), C.byref(img), stream)
                 _CAPACITY_HINT[self.hint_key] = max(_CAPACITY_HINT.get(self.hint_key, 0), grown)
                 if GEOM_CACHE:
                     _GEOM[self.gkey] = _GeomEntry(          # (bin: every field of the binning after num_rendered)
@@ -598,8 +597,7 @@ def _late_handoff(s: _State):
     so = ar.ptr("scratch_out")
     hw = 4 * s.H * s.W
     img = _lib.Image(so, so + 3 * hw, so + 4 * hw, so + 7 * hw, ar.ptr("final_T"), ar.ptr("n_contrib"), *(ar.ptr(n) for n in _HANDOFF))
-    _lib.check(lib.texgs_render_forward(C.byref(s.frame), C.byref(s.inputs), C.byref(s.geom), C.byref(s.bin), C.byref(img), stream),
-               "texgs_render_forward (late hand-off)")
+    _lib.call(lib.texgs_render_forward, C.byref(s.frame), C.byref(s.inputs), C.byref(s.geom), C.byref(s.bin), C.byref(img), stream)
     s.tensors._arenas = tuple(s.tensors._arenas) + (ar,)
     for n in _HANDOFF:
         setattr(s.img, n, ar.ptr(n))
@@ -700,11 +698,11 @@ def backward_raw(s: _State, dL_dcolor, dL_ddepth, dL_dnorm, dL_dalpha, sinks=Non
                            _ptr(bins.base) if bins else None, bins.cap if bins else 0, mask)
         refs = [C.byref(x) for x in (s.frame, s.inputs, s.geom, s.bin, s.img, grads)]
         if before_accumulate is None:
-            _lib.check(lib.texgs_backward(*refs, stream), "texgs_backward")
+            _lib.call(lib.texgs_backward, *refs, stream)
         else:
-            _lib.check(lib.texgs_backward_render(*refs, stream), "texgs_backward_render")
+            _lib.call(lib.texgs_backward_render, *refs, stream)
             before_accumulate()
-            _lib.check(lib.texgs_backward_preprocess(*refs[:3], refs[5], stream), "texgs_backward_preprocess")
+            _lib.call(lib.texgs_backward_preprocess, *refs[:3], refs[5], stream)
     if bins is not None:
         bins.after_call()
         sc.bins = bins
@@ -855,8 +853,7 @@ class GaussianRasterizer(nn.Module):
         vis = torch.zeros(N, dtype=torch.uint8, device=positions.device)
         stream = torch.cuda.current_stream(positions.device).cuda_stream
         with torch.cuda.device(positions.device):
-            _lib.check(lib.texgs_mark_visible(C.byref(frame), positions.data_ptr(), vis.data_ptr(), stream),
-                       "texgs_mark_visible")
+            _lib.call(lib.texgs_mark_visible, C.byref(frame), positions.data_ptr(), vis.data_ptr(), stream)
         return vis.bool()
 
     def prefetch(self, means3D, means2D, opacities, shs=None, scales=None, rotations=None, uvs=None,

@@ -22,6 +22,7 @@ from torch import nn
 import torch.nn.functional as F
 
 from . import _lib
+from .losses import depth2world      # (models/uv_map_gaussian3d.py:155-165 is the same function as texture_gaussian3d.py:299-309)
 from .uvnet import HIDDEN, _tn, unpack_tcnn_params
 
 # configs/uv_map.yaml inv_uv_net_cfg.pre_mlp_cfg.hash_grid_cfg + the constants of models/modules/utils.py:13-14
@@ -83,10 +84,8 @@ class _HashGrid(torch.autograd.Function):
         st = _grid_struct(grid)
         N = x.shape[0]
         enc = torch.empty(N, int(grid["n_levels"]) * _lib.HASHGRID_FEATURES, dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            stream = torch.cuda.current_stream(x.device).cuda_stream
-            _lib.check(lib.texgs_hashgrid_forward(C.byref(st), params.data_ptr(), x.data_ptr(), N, enc.data_ptr(), stream),
-                       "texgs_hashgrid_forward")
+        with _lib.on(x.device) as stream:
+            _lib.call(lib.texgs_hashgrid_forward, C.byref(st), params.data_ptr(), x.data_ptr(), N, enc.data_ptr(), stream)
         ctx.grid = grid
         ctx.save_for_backward(x, params)
         return enc
@@ -103,13 +102,11 @@ class _HashGrid(torch.autograd.Function):
         g = _aligned(g)
         d_p = torch.zeros_like(params) if need_p else None
         d_x = torch.empty_like(x) if need_x else None
-        with torch.cuda.device(x.device):
-            stream = torch.cuda.current_stream(x.device).cuda_stream
+        with _lib.on(x.device) as stream:
             temp = torch.empty(max(1, lib.texgs_hashgrid_backward_temp_bytes(C.byref(st), N)) if need_x else 1, dtype=torch.uint8,
                                device=x.device)
-            p = lambda t: None if t is None else t.data_ptr()
-            _lib.check(lib.texgs_hashgrid_backward(C.byref(st), p(params), p(x), p(g), N, p(d_p), p(d_x), p(temp), stream),
-                       "texgs_hashgrid_backward")
+            p = _lib.ptr
+            _lib.call(lib.texgs_hashgrid_backward, C.byref(st), p(params), p(x), p(g), N, p(d_p), p(d_x), p(temp), stream)
         return d_x, d_p, None
 
 
@@ -262,11 +259,9 @@ def nearest_neighbours(a, b):
         raise ValueError("chamfer_distance: the other point set is empty")
     d2 = torch.empty(P, dtype=torch.float32, device=a.device)
     idx = torch.empty(P, dtype=torch.int32, device=a.device)
-    with torch.cuda.device(a.device):
-        stream = torch.cuda.current_stream(a.device).cuda_stream
+    with _lib.on(a.device) as stream:
         temp = torch.empty(max(1, lib.texgs_chamfer_nn_temp_bytes(P)), dtype=torch.uint8, device=a.device)
-        _lib.check(lib.texgs_chamfer_nn(a.data_ptr(), P, b.data_ptr(), Q, d2.data_ptr(), idx.data_ptr(), temp.data_ptr(), stream),
-                   "texgs_chamfer_nn")
+        _lib.call(lib.texgs_chamfer_nn, a.data_ptr(), P, b.data_ptr(), Q, d2.data_ptr(), idx.data_ptr(), temp.data_ptr(), stream)
     return d2, idx.long()
 
 
@@ -311,19 +306,6 @@ def chamfer_distance(x, y, single_directional=False):
 
 
 # ---- stage-2 losses --------------------------------------------------------------------------------------------------------
-def depth2world(depth, full_proj_transform, zfar, znear):
-    """models/uv_map_gaussian3d.py:155-165: per-pixel world position [H, W, 3] of a depth map [H, W]."""
-    H, W = depth.shape
-    pix_x = torch.arange(W, device=depth.device)
-    pix_y = torch.arange(H, device=depth.device)
-    ndc_x = (pix_x * 2 + 1) / W - 1.0
-    ndc_y = (pix_y * 2 + 1) / H - 1.0
-    ndc_y, ndc_x = torch.meshgrid(ndc_y, ndc_x, indexing="ij")
-    xyz = torch.stack([ndc_x * depth, ndc_y * depth, zfar * depth / (zfar - znear) - zfar * znear / (zfar - znear)], dim=-1).reshape(-1, 3)
-    xyz = torch.cat([xyz, depth.reshape(-1, 1)], dim=-1) @ torch.linalg.inv(full_proj_transform)
-    return xyz[:, :3].reshape(H, W, 3)
-
-
 @torch.no_grad()
 def render_depth_alpha(settings, means3D, opacities, scales, rotations):
     """The stage-2 render (uv_map_gaussian3d.py:171-176): the untextured diff_gauss forward with colors_precomp = 0, no graph

@@ -186,22 +186,21 @@ class UVNet(nn.Module):
         x = xyz.detach().to(dtype=torch.float32).contiguous()
         N = x.shape[0]
         ws = self._kernel_args(dev, emb)
-        p = lambda t: None if t is None else t.data_ptr()
+        p = _lib.ptr
         net = _lib.UVNetStruct(*[p(t) for t in ws], HIDDEN)
-        stream = torch.cuda.current_stream(dev).cuda_stream
         prec = _lib.UV_PRECISION[self.precision]
         key = tuple((t.data_ptr(), t._version) for t in (self.pre_mlp[2].weight, self.mlp[0].weight, self.mlp[2].weight)) + (dev, prec)
         uvs = torch.empty(N, 3, dtype=torch.float32, device=dev)
         juv = torch.empty(N, 9, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
+        with _lib.on(dev) as stream:
             slot = (dev.index, int(stream))
             ent = self._packed.get(slot)
             if ent is None or ent[0] != key:
                 nbytes = lib.texgs_uv_packed_bytes(prec)           # ("mixed" holds both layouts)
                 buf = ent[1] if ent is not None and ent[1].numel() == nbytes else torch.empty(nbytes, dtype=torch.uint8, device=dev)
-                _lib.check(lib.texgs_uv_pack(C.byref(net), prec, p(buf), stream), "texgs_uv_pack")       # (re-packed in place: same stream, in order)
+                _lib.call(lib.texgs_uv_pack, C.byref(net), prec, p(buf), stream)       # (re-packed in place: same stream, in order)
                 self._packed[slot] = ent = (key, buf)
-            _lib.check(lib.texgs_uv_taylor_packed(C.byref(net), prec, p(ent[1]), p(x), N, p(uvs), p(juv), stream), "texgs_uv_taylor_packed")
+            _lib.call(lib.texgs_uv_taylor_packed, C.byref(net), prec, p(ent[1]), p(x), N, p(uvs), p(juv), stream)
         return uvs, juv
 
     @torch.no_grad()
@@ -220,19 +219,18 @@ class UVNet(nn.Module):
         if gg.shape != (N, 3):
             raise ValueError(f"g must be [N, 3], got {tuple(gg.shape)}")
         ws = self._kernel_args(dev, emb, params)
-        p = lambda t: None if t is None else t.data_ptr()
+        p = _lib.ptr
         netp = _lib.UVNetStruct(*[p(t) for t in ws], HIDDEN)
         shapes = [(HIDDEN, 3), (HIDDEN,), (HIDDEN, HIDDEN), (HIDDEN,), (HIDDEN, HIDDEN), (HIDDEN,), (HIDDEN, HIDDEN), (HIDDEN,),
                   (3, HIDDEN), (3,)]
         outs = [torch.empty(sh, dtype=torch.float32, device=dev) for sh in shapes]
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
+        with _lib.on(dev) as stream:
             temp = torch.empty(lib.texgs_uv_backward_temp_bytes(N), dtype=torch.uint8, device=dev)
             gr = _lib.UVNetGradStruct(*[p(t) for t in outs])
             # precision "fp32": all nine GEMMs on the f32-input MFMA; "mixed" / "bf16x3": the forward recomputation in f32 (the
             # forward launch's ReLU masks bit for bit), the six GEMMs of the backward chain as split-bf16 products (~1e-5 relative)
             prec = _lib.UV_PRECISION[self.precision]
-            _lib.check(lib.texgs_uv_backward(C.byref(netp), prec, p(x), p(gg), N, C.byref(gr), p(temp), stream), "texgs_uv_backward")
+            _lib.call(lib.texgs_uv_backward, C.byref(netp), prec, p(x), p(gg), N, C.byref(gr), p(temp), stream)
         return outs
 
     def uvs_and_jacobian_with_grad(self, xyz, emb):
