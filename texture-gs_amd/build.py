@@ -2,7 +2,8 @@
 
 Objects are rebuilt only when their sources are newer.  preprocess.hip is built with -ffp-contract=off (its
 fp32 operation order is part of the bit-exact key/rect/radius contract) and so is points.hip (its squared distance is
-compared bit for bit), density.hip (its per-step statistics likewise) and metrics.hip (its fp64 sums are compared with numpy's);
+compared bit for bit), density.hip (its per-step statistics likewise), optim.hip (the Adam step's arithmetic likewise) and
+metrics.hip (its fp64 sums are compared with numpy's);
 the render kernels allow contraction
 and use hardware fp32 atomics (-munsafe-fp-atomics).
 """
@@ -34,19 +35,21 @@ UNITS = {
     "cubetex.hip": ["-munsafe-fp-atomics"],   # the texture gradient's scatter: hardware fp32 atomic adds
     "density.hip": ["-ffp-contract=off"],     # the per-step statistics are a bit-exact contract: x*x + y*y with separate roundings
     "metrics.hip": ["-ffp-contract=off"],     # fp64 sums of exact fp32 products, reproducible against numpy: no fused multiply-add
+    "optim.hip": ["-ffp-contract=off"],       # the Adam step's arithmetic is a bit-exact contract: one rounding per operation
     "abi.hip": [],
 }
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "wave_ops.h"), os.path.join(CSRC, "render_bwd_body.h"),
-           os.path.join(ROOT, "include", "texgs.h")]
+           os.path.join(ROOT, "include", "texgs.h"), os.path.join(ROOT, "include", "texgs_optim.h")]
 
 
 def build_id():
-    """Identity of what libtexgs.so is built FROM: sha256 over csrc/*, include/texgs.h and the compile flags (16 hex digits).
+    """Identity of what libtexgs.so is built FROM: sha256 over csrc/*, include/texgs.h, include/texgs_optim.h and the compile flags (16 hex digits).
     build() bakes it into the library (texgs_build_id()); texgs/_lib.py recomputes it from the tree and refuses a library that
     was built from other sources -- the prebuilt .so is what travels to the GPU box, mtimes do not."""
     import hashlib
     h = hashlib.sha256()
-    files = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))) + [os.path.join(ROOT, "include", "texgs.h")]
+    files = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))) \
+        + [os.path.join(ROOT, "include", "texgs.h"), os.path.join(ROOT, "include", "texgs_optim.h")]
     for f in files:
         h.update(os.path.basename(f).encode())
         h.update(open(f, "rb").read())

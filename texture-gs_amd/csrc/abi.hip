@@ -539,6 +539,27 @@ int texgs_eval_metrics(const float* image, const float* gt_image, const float* n
     return launched("eval_metrics", launch_eval_metrics(image, gt_image, norm, gt_norm, alpha, H, W, clamp01 != 0, temp, row, s), s, false);
 }
 
+// include/texgs_optim.h: every record is checked before the first launch, so a refused call has changed nothing
+int texgs_adam_step(const TexGSAdamTensor* tensors, int32_t count, int32_t zero_grads, void* stream) {
+    if (count < 0) return fail_msg("count < 0");
+    if (count == 0) return 0;
+    if (!tensors) return fail_msg("tensors is NULL");
+    for (int32_t k = 0; k < count; ++k) {
+        const TexGSAdamTensor& t = tensors[k];
+        if (t.numel < 0) return fail_msg("numel < 0");
+        if (t.numel == 0) continue;
+        if (!t.p || !t.g || !t.m || !t.v) return fail_msg("NULL pointer (p, g, m or v) in a record with numel > 0");
+        if (((uintptr_t)t.p | (uintptr_t)t.g | (uintptr_t)t.m | (uintptr_t)t.v) & 3)
+            return fail_msg("p, g, m and v must be 4-byte aligned");
+    }
+    hipStream_t s = (hipStream_t)stream;
+    for (int32_t first = 0; first < count; first += TEXGS_ADAM_MAX_TENSORS) {
+        const int32_t n = count - first < TEXGS_ADAM_MAX_TENSORS ? count - first : TEXGS_ADAM_MAX_TENSORS;
+        if (int r = launched("adam_step", launch_adam_step(tensors + first, n, zero_grads, s), s, false)) return r;
+    }
+    return 0;
+}
+
 int texgs_selftest_waveops(const float* seed128, float* out576, void* stream) {
     if (!seed128 || !out576) return fail_msg("NULL argument");
     return launched("selftest_waveops", launch_selftest_waveops(seed128, out576, (hipStream_t)stream), (hipStream_t)stream, false);

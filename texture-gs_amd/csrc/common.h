@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "texgs.h"
+#include "texgs_optim.h"
 
 // ---- operator constants (restated in oracle/texgs_torch.py) ----
 #define TG_NEAR_Z        0.2f
@@ -123,3 +124,4 @@ hipError_t launch_density_move(const TexGSDensityMove* m, hipStream_t s);
 size_t eval_metrics_temp_bytes(int H, int W);
 hipError_t launch_eval_metrics(const float* image, const float* gt_image, const float* norm, const float* gt_norm, const float* alpha, int H,
                         int W, int clamp01, void* temp, double* row, hipStream_t s);
+hipError_t launch_adam_step(const TexGSAdamTensor* tensors, int count, int zero_grads, hipStream_t s);
