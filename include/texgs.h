@@ -202,6 +202,12 @@ typedef struct TexGSGrads {
     int32_t accumulate;        /* bit mask (TEXGS_ACC_*): K8 ADDS into the per-Gaussian outputs whose bit is set (fused gradient
                                   accumulation of a multi-view step, or straight into a leaf's existing .grad; culled Gaussians
                                   write nothing there) and overwrites the others.  dL_dtexture is always accumulated into.   */
+    float* dL_dvd_residue;     /* f32[N,3] or NULL (the default).  Set: K8 leaves the view-dependent colour's chain to shs and to the
+                                  view direction undone -- it stages no SH rows, does not touch dL_dshs and uses no LDS -- and stores
+                                  dL/dvd here instead (zeros for a culled Gaussian and for a view without an active SH band);
+                                  texgs_sh_flush (texgs_multiview.h) does that chain for several views at once.  Needs
+                                  TEXGS_ACC_SHS and TEXGS_ACC_MEANS3D in `accumulate`: the flush adds into both.  Appended to the
+                                  struct: a caller that zero-fills TexGSGrads gets the old behaviour.                        */
 } TexGSGrads;
 
 int         texgs_abi_version(void);

@@ -20,8 +20,9 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-# kernel name fragment -> bench.py kernel group (texgs.h TEXGS_K_*); k_bin_offsets is launched inside the render_bwd bracket
-GROUPS = (("k_render_fwd", "render_fwd"), ("k_render_bwd", "render_bwd"), ("k_bin_offsets", "render_bwd"), ("k_preprocess_fwd", "preprocess_fwd"),
+# kernel name fragment -> bench.py kernel group (texgs.h TEXGS_K_*); k_bin_offsets is launched inside the render_bwd bracket; k_sh_flush
+# (once per multi-view step: K8's deferred SH step) is counted with K8, so that preprocess_bwd stays the backward preprocess per view
+GROUPS = (("k_sh_flush", "preprocess_bwd"), ("k_render_fwd", "render_fwd"), ("k_render_bwd", "render_bwd"), ("k_bin_offsets", "render_bwd"), ("k_preprocess_fwd", "preprocess_fwd"),
           ("k_preprocess_bwd", "preprocess_bwd"), ("k_texgrad_reduce", "texgrad_reduce"), ("k_duplicate", "duplicate"),
           ("k_ranges", "ranges"), ("k_tile_order", "ranges"), ("k_depth_", "scan"), ("k_group_prefix", "duplicate"), ("k_radix_", "sort"))
 

@@ -15,4 +15,4 @@ rocprofv3 --pmc SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VMEM SQ_IN
 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $OUT/pmc3 -o pmc3 --output-format csv -- python $R/bench.py $PMC > $OUT/bench_pmc3.log 2>&1
 rocprofv3 --pmc WRITE_SIZE TCC_HIT_sum TCC_MISS_sum --kernel-trace -d $OUT/pmc4 -o pmc4 --output-format csv -- python $R/bench.py $PMC > $OUT/bench_pmc4.log 2>&1
 find $OUT -name "*.csv" | head -30
-tail -2 $OUT/bench_trace.log $OUT/bench_trace_serial.log $OUT/bench_pmc1.log
+for f in $OUT/bench_trace.log $OUT/bench_trace_serial.log $OUT/bench_pmc1.log; do tail -n 2 $f; done

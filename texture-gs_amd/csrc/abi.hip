@@ -230,6 +230,8 @@ int texgs_backward_preprocess(const TexGSFrame* frame, const TexGSInputs* in, co
     if (!(grads->want & TEXGS_WANT_GAUSSIANS)) return 0;          // nobody reads a per-Gaussian gradient: K7 summed no moments either
     if (!grads->acc) return fail_msg("acc must be allocated");
     if (in->cov3D_precomp && !grads->dL_dcov3D) return fail_msg("dL_dcov3D is required with cov3D_precomp");
+    if (grads->dL_dvd_residue && (grads->accumulate & (TEXGS_ACC_SHS | TEXGS_ACC_MEANS3D)) != (TEXGS_ACC_SHS | TEXGS_ACC_MEANS3D))
+        return fail_msg("dL_dvd_residue needs TEXGS_ACC_SHS and TEXGS_ACC_MEANS3D in accumulate: texgs_sh_flush adds into both");
     hipStream_t s = (hipStream_t)stream;
     const CamConst c = make_cam(frame);
     hipError_t st;
@@ -558,6 +560,30 @@ int texgs_adam_step(const TexGSAdamTensor* tensors, int32_t count, int32_t zero_
         if (int r = launched("adam_step", launch_adam_step(tensors + first, n, zero_grads, s), s, false)) return r;
     }
     return 0;
+}
+
+// include/texgs_multiview.h: every record is checked before the launch, so a refused call has changed nothing
+int texgs_sh_flush(int32_t N, int32_t K, const float* means3D, const float* shs, float* dL_dshs, float* dL_dmeans3D,
+                   const TexGSShFlushView* views, int32_t count, void* stream) {
+    if (count < 0) return fail_msg("count < 0");
+    if (count > TEXGS_SH_FLUSH_MAX_VIEWS) return fail_msg("count exceeds TEXGS_SH_FLUSH_MAX_VIEWS: flush in several calls");
+    if (N < 0) return fail_msg("N < 0");
+    if (count == 0 || N == 0) return 0;
+    if (!dL_dshs || !dL_dmeans3D) return fail_msg("NULL sink (dL_dshs or dL_dmeans3D) with views pending");
+    if (!means3D || !shs || !views) return fail_msg("NULL argument (means3D, shs or views) with views pending");
+    if (K < 1 || K > 16) return fail_msg("K must be in [1,16]");
+    for (int32_t k = 0; k < count; ++k) {
+        const TexGSShFlushView& v = views[k];
+        if (!v.campos || !v.residue) return fail_msg("NULL campos or residue in a view record");
+        if (v.sh_degree < 0 || v.sh_degree > 3) return fail_msg("sh_degree of a view record must be in [0,3]");
+        if (v.sh_coeffs != K) {
+            snprintf(g_err, sizeof(g_err), "K does not match: view %d wrote its residue with K = %d, the flush has K = %d", (int)k,
+                     (int)v.sh_coeffs, (int)K);
+            return -1;
+        }
+    }
+    hipStream_t s = (hipStream_t)stream;
+    return launched("sh_flush", launch_sh_flush(N, K, means3D, shs, dL_dshs, dL_dmeans3D, views, count, s), s, false);
 }
 
 int texgs_selftest_waveops(const float* seed128, float* out576, void* stream) {

@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include "texgs.h"
 #include "texgs_optim.h"
+#include "texgs_multiview.h"
 
 // ---- operator constants (restated in oracle/texgs_torch.py) ----
 #define TG_NEAR_Z        0.2f
@@ -67,6 +68,8 @@ struct LaunchStatus {
 hipError_t launch_preprocess_fwd(const CamConst& c, const TexGSFrame* f, const TexGSInputs* in, TexGSGeom* g, hipStream_t s);
 hipError_t launch_preprocess_bwd(const CamConst& c, const TexGSFrame* f, const TexGSInputs* in, const TexGSGeom* g,
                            TexGSGrads* gr, hipStream_t s);
+hipError_t launch_sh_flush(int N, int K, const float* means3D, const float* shs, float* dL_dshs, float* dL_dmeans3D,
+                           const TexGSShFlushView* views, int count, hipStream_t s);
 hipError_t launch_mark_visible(const TexGSFrame* f, const float* means3D, uint8_t* visible, hipStream_t s);
 hipError_t launch_depth_sort_scan(const TexGSGeom* g, int N, hipStream_t s);
 uint32_t* bin_block_sums_ptr(const TexGSGeom* g, int N);

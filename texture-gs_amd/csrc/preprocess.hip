@@ -81,6 +81,15 @@ __device__ __forceinline__ void smallest_eigvec(const float* S6, float* n) {
     n[2] = (k == 0) ? v20 : ((k == 1) ? v21 : v22);
 }
 
+// Unit view direction of a Gaussian: raw = mean - camera position, dir = raw / |raw|; returns |raw|.  The ONE definition K1, K8 and the
+// deferred SH flush (k_sh_flush) share: the flush's dL/dSH rows are bit-identical to K8's only because all three round alike.
+__device__ __forceinline__ float view_direction(const float* m, const float* cam, float* raw, float* dir) {
+    raw[0] = m[0] - cam[0]; raw[1] = m[1] - cam[1]; raw[2] = m[2] - cam[2];
+    const float dlen = sqrtf(raw[0] * raw[0] + raw[1] * raw[1] + raw[2] * raw[2]);
+    dir[0] = raw[0] / dlen; dir[1] = raw[1] / dlen; dir[2] = raw[2] / dlen;
+    return dlen;
+}
+
 // COV: the world covariance is an input (cov6 = TexGSInputs.cov3D_precomp) -- a compile-time flavour so that the common path
 // carries neither the branch nor the eigenvector code (K1 went 36 -> 64 us when it did)
 template <bool COV = false>
@@ -172,7 +181,8 @@ __device__ __forceinline__ void geo_forward(Geo& g, const Frame& F, const CamCon
     g.radius = (int)ceilf(3.0f * sqrtf(lam));
 
     // normal: shortest axis (first minimum), flipped to face the camera, world space
-    g.dir[0] = mx - F.cam[0]; g.dir[1] = my - F.cam[1]; g.dir[2] = mz - F.cam[2];
+    float raw[3];
+    g.dlen = view_direction(g.m, F.cam, raw, g.dir);
     float n0, n1, n2;
     if constexpr (COV) {
         float ev[3];
@@ -187,10 +197,8 @@ __device__ __forceinline__ void geo_forward(Geo& g, const Frame& F, const CamCon
         n1 = (g.kmin == 0) ? g.R[3] : ((g.kmin == 1) ? g.R[4] : g.R[5]);      // keeps R[] in registers
         n2 = (g.kmin == 0) ? g.R[6] : ((g.kmin == 1) ? g.R[7] : g.R[8]);
     }
-    g.sign = ((n0 * g.dir[0] + n1 * g.dir[1] + n2 * g.dir[2]) > 0.0f) ? -1.0f : 1.0f;
+    g.sign = ((n0 * raw[0] + n1 * raw[1] + n2 * raw[2]) > 0.0f) ? -1.0f : 1.0f;
     g.n[0] = g.sign * n0; g.n[1] = g.sign * n1; g.n[2] = g.sign * n2;
-    g.dlen = sqrtf(g.dir[0] * g.dir[0] + g.dir[1] * g.dir[1] + g.dir[2] * g.dir[2]);
-    g.dir[0] /= g.dlen; g.dir[1] /= g.dlen; g.dir[2] /= g.dlen;
 
     // UV Taylor pre-fold: uv(p) = phi + G dp / (1 + g.dp), dp = pix - xy   
 #pragma unroll
@@ -459,8 +467,15 @@ k_preprocess_fwd(CamConst C, const float* __restrict__ vm, const float* __restri
 #ifndef K8_BLOCK
 #define K8_BLOCK 256
 #endif
-template <bool COV>
-__global__ void __launch_bounds__(K8_BLOCK)
+// The block size of the DEFER flavour (no LDS, so nothing ties it to K8_BLOCK)
+#ifndef K8_DEFER_BLOCK
+#define K8_DEFER_BLOCK 256
+#endif
+// DEFER (TexGSGrads.dL_dvd_residue): the view-dependent colour's chain to shs and to the view direction -- step (10) -- is left to
+// k_sh_flush, once per multi-view step.  This flavour hands on dL/dvd (three floats per Gaussian), stages no SH rows, does not touch
+// dL_dshs and uses no LDS.  A compile-time flavour: the immediate one is the code it was.
+template <bool COV, bool DEFER, int BLOCK>
+__global__ void __launch_bounds__(BLOCK)
 k_preprocess_bwd(CamConst C, const float* __restrict__ vm, const float* __restrict__ pm, const float* __restrict__ cp,
                  const float* __restrict__ means, const float* __restrict__ shs, const float* __restrict__ opac,
                  const float* __restrict__ scales,
@@ -468,18 +483,20 @@ k_preprocess_bwd(CamConst C, const float* __restrict__ vm, const float* __restri
                  const int32_t* __restrict__ radii, float* __restrict__ acc,
                  float* __restrict__ d_means, float* __restrict__ d_means2D, float* __restrict__ d_shs,
                  float* __restrict__ d_op, float* __restrict__ d_scales, float* __restrict__ d_rots,
-                 float* __restrict__ d_uvs, float* __restrict__ d_coff, float* __restrict__ d_cov6, int accumulate) {
+                 float* __restrict__ d_uvs, float* __restrict__ d_coff, float* __restrict__ d_cov6, float* __restrict__ d_vd_res,
+                 int accumulate) {
     extern __shared__ __attribute__((aligned(16))) float s_sh[];          // [256][3K]: SH rows in, dL/dSH rows out
-    const int i = blockIdx.x * K8_BLOCK + threadIdx.x;
+    const int i = blockIdx.x * BLOCK + threadIdx.x;
     const int K = C.sh_coeffs;
     const bool live = i < C.N;
     const int row = 3 * K;
     const int na = (shs != nullptr && C.sh_degree > 0) ? sh_active(C.sh_degree, K) : 0;
-    const size_t first = (size_t)blockIdx.x * K8_BLOCK * row;
-    const int count = d_shs ? (int)min((size_t)K8_BLOCK * row, (size_t)C.N * row - first) : 0;
+    const size_t first = (size_t)blockIdx.x * BLOCK * row;
+    const int count = d_shs ? (int)min((size_t)BLOCK * row, (size_t)C.N * row - first) : 0;
     const bool vec = d_shs && (((size_t)d_shs) & 15) == 0;
-    if (na > 0 && d_shs) {
-        for (int k = threadIdx.x; k < count; k += K8_BLOCK) s_sh[k] = shs[first + k];      // plain loads: the compiler batches them
+    if constexpr (DEFER) { (void)first; (void)count; (void)vec; }
+    if (!DEFER && na > 0 && d_shs) {
+        for (int k = threadIdx.x; k < count; k += BLOCK) s_sh[k] = shs[first + k];      // plain loads: the compiler batches them
         __syncthreads();
     }
     const bool visible = live && radii[i] > 0;
@@ -495,6 +512,7 @@ k_preprocess_bwd(CamConst C, const float* __restrict__ vm, const float* __restri
         }
         if (d_uvs && !(accumulate & TEXGS_ACC_UVS)) d_uvs[3 * i] = d_uvs[3 * i + 1] = d_uvs[3 * i + 2] = 0.f;
         if (d_coff && !(accumulate & TEXGS_ACC_COLOR_OFFSET)) d_coff[3 * i] = d_coff[3 * i + 1] = d_coff[3 * i + 2] = 0.f;
+        if constexpr (DEFER) d_vd_res[3 * i] = d_vd_res[3 * i + 1] = d_vd_res[3 * i + 2] = 0.f;
     }
     if (visible) {
 #define OUT(BIT, P, V) do { if (accumulate & (BIT)) (P) += (V); else (P) = (V); } while (0)
@@ -644,7 +662,10 @@ k_preprocess_bwd(CamConst C, const float* __restrict__ vm, const float* __restri
     }
 
     // (10) view-dependent colour -> shs, view direction (rows staged in LDS; dL/dSH overwrites the row in place)
-    if (d_shs && na > 0) {
+    if constexpr (DEFER) {      // handed to k_sh_flush; no active band: the view contributes nothing
+        d_vd_res[3 * i + 0] = (na > 0) ? A[R_VD] : 0.f; d_vd_res[3 * i + 1] = (na > 0) ? A[R_VD + 1] : 0.f;
+        d_vd_res[3 * i + 2] = (na > 0) ? A[R_VD + 2] : 0.f;
+    } else if (d_shs && na > 0) {
         float b[15], bx[15], by[15], bz[15];
 #pragma unroll
         for (int k = 0; k < 15; ++k) { b[k] = 0.f; bx[k] = 0.f; by[k] = 0.f; bz[k] = 0.f; }
@@ -690,14 +711,88 @@ k_preprocess_bwd(CamConst C, const float* __restrict__ vm, const float* __restri
     }
 #undef OUT
     }   // visible
-    if (d_shs) {            // dL/dSH: zero rows for culled Gaussians / inactive degree, then one coalesced block store
+    if constexpr (!DEFER) if (d_shs) {            // dL/dSH: zero rows for culled Gaussians / inactive degree, then one coalesced block store
         if (na == 0 || (live && !visible)) {
             if (live) for (int k = 0; k < row; ++k) s_sh[threadIdx.x * row + k] = 0.f;
         }
         __syncthreads();
-        if (accumulate & TEXGS_ACC_SHS) sh_rows_out<K8_BLOCK, true>(d_shs + first, s_sh, count, vec);
-        else sh_rows_out<K8_BLOCK, false>(d_shs + first, s_sh, count, vec);
+        if (accumulate & TEXGS_ACC_SHS) sh_rows_out<BLOCK, true>(d_shs + first, s_sh, count, vec);
+        else sh_rows_out<BLOCK, false>(d_shs + first, s_sh, count, vec);
     }
+}
+
+// ------------------------------------------------------------------------------------------------ deferred SH flush
+// Step (10) of K8 for up to TEXGS_SH_FLUSH_MAX_VIEWS views at once (include/texgs_multiview.h): the views' K8 ran in the DEFER flavour
+// and left dL/dvd per Gaussian.  One thread per Gaussian.  The workgroup's SH rows are staged through LDS into registers (coalesced
+// read), then the same LDS holds its dL/dSH rows: read once, every view added in the order given, written once.  This file is built
+// with -ffp-contract=off, so `row + b * v` is a rounded product and a rounded sum, as K8's `b * v` into LDS and sh_rows_out's add are:
+// the rows end bit-identical to K8's.  The records travel by value in the kernel arguments (wave-uniform loads).
+constexpr int FL_BLOCK = 256;
+constexpr int FL_MAX = TEXGS_SH_FLUSH_MAX_VIEWS;
+
+struct ShFlushArgs {
+    TexGSShFlushView v[FL_MAX];
+    int32_t count;
+};
+
+__global__ void __launch_bounds__(FL_BLOCK)
+k_sh_flush(ShFlushArgs a, int N, int K, const float* __restrict__ means, const float* __restrict__ shs,
+           float* __restrict__ d_shs, float* __restrict__ d_means) {
+    extern __shared__ __attribute__((aligned(16))) float s_row[];         // [256][3K]: SH rows, then dL/dSH rows
+    const int i = blockIdx.x * FL_BLOCK + threadIdx.x;
+    const bool live = i < N;
+    const int row = 3 * K;
+    const size_t first = (size_t)blockIdx.x * FL_BLOCK * row;
+    const int count = (int)min((size_t)FL_BLOCK * row, (size_t)N * row - first);
+    const bool vec = (((size_t)d_shs) & 15) == 0;
+    for (int k = threadIdx.x; k < count; k += FL_BLOCK) s_row[k] = shs[first + k];
+    __syncthreads();
+    float sp[45];                       // this Gaussian's coefficients of bands 1..3 (at most 15 are ever active)
+#pragma unroll
+    for (int k = 0; k < 45; ++k) sp[k] = (live && k < row) ? s_row[threadIdx.x * row + k] : 0.f;
+    __syncthreads();
+    for (int k = threadIdx.x; k < count; k += FL_BLOCK) s_row[k] = d_shs[first + k];
+    __syncthreads();
+    if (live) {
+        const float m[3] = {means[3 * i + 0], means[3 * i + 1], means[3 * i + 2]};
+        float* gp = s_row + threadIdx.x * row;
+        float dm[3] = {d_means[3 * i + 0], d_means[3 * i + 1], d_means[3 * i + 2]};
+        bool any = false;
+        for (int v = 0; v < a.count; ++v) {
+            const float* __restrict__ res = a.v[v].residue;
+            const float v0 = res[3 * i + 0], v1 = res[3 * i + 1], v2 = res[3 * i + 2];
+            const int deg = a.v[v].sh_degree;
+            const int na = deg > 0 ? sh_active(deg, K) : 0;
+            if ((v0 == 0.f && v1 == 0.f && v2 == 0.f) || na == 0) continue;     // culled in that view, or no gradient reached it
+            const float* __restrict__ cp = a.v[v].campos;
+            const float cam[3] = {cp[0], cp[1], cp[2]};
+            float raw[3], dir[3];
+            const float dlen = view_direction(m, cam, raw, dir);
+            float b[15], bx[15], by[15], bz[15];
+#pragma unroll
+            for (int k = 0; k < 15; ++k) { b[k] = 0.f; bx[k] = 0.f; by[k] = 0.f; bz[k] = 0.f; }
+            sh_basis(deg, dir[0], dir[1], dir[2], b);
+            sh_basis_grad(deg, dir[0], dir[1], dir[2], bx, by, bz);
+            float ddx = 0.f, ddy = 0.f, ddz = 0.f;
+#pragma unroll
+            for (int k = 0; k < 15; ++k) {
+                if (k < na) {
+                    const float w = sp[3 * k + 0] * v0 + sp[3 * k + 1] * v1 + sp[3 * k + 2] * v2;
+                    ddx += bx[k] * w; ddy += by[k] * w; ddz += bz[k] * w;
+                    gp[3 * k + 0] = gp[3 * k + 0] + b[k] * v0; gp[3 * k + 1] = gp[3 * k + 1] + b[k] * v1;
+                    gp[3 * k + 2] = gp[3 * k + 2] + b[k] * v2;
+                }
+            }
+            const float dd = dir[0] * ddx + dir[1] * ddy + dir[2] * ddz;
+            dm[0] += (ddx - dir[0] * dd) / dlen;
+            dm[1] += (ddy - dir[1] * dd) / dlen;
+            dm[2] += (ddz - dir[2] * dd) / dlen;
+            any = true;
+        }
+        if (any) { d_means[3 * i + 0] = dm[0]; d_means[3 * i + 1] = dm[1]; d_means[3 * i + 2] = dm[2]; }
+    }
+    __syncthreads();
+    sh_rows_out<FL_BLOCK, false>(d_shs + first, s_row, count, vec);
 }
 
 // ------------------------------------------------------------------------------------------------ K9
@@ -729,14 +824,31 @@ hipError_t launch_preprocess_fwd(const CamConst& c, const TexGSFrame* f, const T
 hipError_t launch_preprocess_bwd(const CamConst& c, const TexGSFrame* f, const TexGSInputs* in, const TexGSGeom* g,
                            TexGSGrads* gr, hipStream_t s) {
     if (c.N <= 0) return hipSuccess;
-    const int blocks = (c.N + K8_BLOCK - 1) / K8_BLOCK;
-    const size_t lds = gr->dL_dshs ? (size_t)K8_BLOCK * 3 * c.sh_coeffs * sizeof(float) : 0;
-#define K8_LAUNCH(COV) hipLaunchKernelGGL(k_preprocess_bwd<COV>, dim3(blocks), dim3(K8_BLOCK), lds, s, c, f->viewmatrix, f->projmatrix, f->campos, \
+#define K8_LAUNCH(COV, DEFER, BLOCK, LDS) hipLaunchKernelGGL((k_preprocess_bwd<COV, DEFER, BLOCK>), dim3((c.N + BLOCK - 1) / BLOCK), dim3(BLOCK), LDS, s, \
+                       c, f->viewmatrix, f->projmatrix, f->campos, \
                        in->means3D, in->shs, in->opacities, in->scales, in->rotations, in->gradient_uvs, in->cov3D_precomp, \
                        g->radii, gr->acc, gr->dL_dmeans3D, gr->dL_dmeans2D, gr->dL_dshs, gr->dL_dopacities, gr->dL_dscales, \
-                       gr->dL_drotations, gr->dL_duvs, gr->dL_dcolor_offset, gr->dL_dcov3D, gr->accumulate)
-    if (in->cov3D_precomp) K8_LAUNCH(true); else K8_LAUNCH(false);
+                       gr->dL_drotations, gr->dL_duvs, gr->dL_dcolor_offset, gr->dL_dcov3D, gr->dL_dvd_residue, gr->accumulate)
+    if (gr->dL_dvd_residue) {       // step (10) deferred to the flush: no SH rows, no LDS
+        if (in->cov3D_precomp) K8_LAUNCH(true, true, K8_DEFER_BLOCK, 0); else K8_LAUNCH(false, true, K8_DEFER_BLOCK, 0);
+    } else {
+        const size_t lds = gr->dL_dshs ? (size_t)K8_BLOCK * 3 * c.sh_coeffs * sizeof(float) : 0;
+        if (in->cov3D_precomp) K8_LAUNCH(true, false, K8_BLOCK, lds); else K8_LAUNCH(false, false, K8_BLOCK, lds);
+    }
 #undef K8_LAUNCH
+    return hipGetLastError();
+}
+
+// `count` <= TEXGS_SH_FLUSH_MAX_VIEWS records, K <= 16 (checked by the caller, abi.hip)
+hipError_t launch_sh_flush(int N, int K, const float* means3D, const float* shs, float* dL_dshs, float* dL_dmeans3D,
+                           const TexGSShFlushView* views, int count, hipStream_t s) {
+    if (count < 0 || count > FL_MAX) return hipErrorInvalidValue;
+    if (N <= 0 || count == 0) return hipSuccess;
+    ShFlushArgs a;
+    for (int k = 0; k < FL_MAX; ++k) a.v[k] = k < count ? views[k] : TexGSShFlushView{nullptr, nullptr, 0, 0};
+    a.count = count;
+    const size_t lds = (size_t)FL_BLOCK * 3 * K * sizeof(float);
+    hipLaunchKernelGGL(k_sh_flush, dim3((N + FL_BLOCK - 1) / FL_BLOCK), dim3(FL_BLOCK), lds, s, a, N, K, means3D, shs, dL_dshs, dL_dmeans3D);
     return hipGetLastError();
 }
 

@@ -53,7 +53,7 @@ class Grads(C.Structure):
                 ("dL_dscales", _fp), ("dL_drotations", _fp), ("dL_duvs", _fp), ("dL_dtexture", _fp),
                 ("dL_dcolor_offset", _fp), ("dL_dcov3D", _fp), ("want", C.c_uint32), ("tex_bins", _fp), ("tex_bin_cursor", _fp), ("tex_bin_base", _fp),
                 ("tex_rec_cap", C.c_uint32),
-                ("accumulate", C.c_int32)]
+                ("accumulate", C.c_int32), ("dL_dvd_residue", _fp)]
 
 
 class UVNetStruct(C.Structure):

@@ -11,9 +11,39 @@ end-of-step work --, the per-Gaussian gradients after the last K8; the compute s
 gradients are read (GradBucket.wait).  Views are dealt to ranks by estimated cost (lpt_shard_views), not round-robin:
 the step ends with the slowest rank.
 """
+import ctypes as C
 from typing import List, Sequence
 
 import torch
+
+SH_FLUSH_MAX_VIEWS = 16         # TEXGS_SH_FLUSH_MAX_VIEWS: view records of one texgs_sh_flush launch
+
+
+class ShFlushView(C.Structure):
+    """ctypes mirror of TexGSShFlushView (include/texgs_multiview.h), 24 bytes"""
+    _fields_ = [("campos", C.c_void_p), ("residue", C.c_void_p), ("sh_degree", C.c_int32), ("sh_coeffs", C.c_int32)]
+
+
+# (restype, argtypes) of `int texgs_sh_flush(int32_t N, int32_t K, const float* means3D, const float* shs, float* dL_dshs,
+#  float* dL_dmeans3D, const TexGSShFlushView* views, int32_t count, void* stream)`
+SH_FLUSH_SIGNATURE = (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ShFlushView), C.c_int32,
+                                C.c_void_p])
+_sh_flush_fn = None
+
+
+def sh_flush_entry():
+    """texgs_sh_flush of the loaded library with its signature applied (on first use)"""
+    global _sh_flush_fn
+    if _sh_flush_fn is None:
+        from . import _lib
+        lib = _lib.load()
+        if not hasattr(lib, "texgs_sh_flush"):
+            raise RuntimeError(f"libtexgs.so at {_lib.LIB_PATH} does not export texgs_sh_flush; rebuild it with "
+                               "`python texture-gs_amd/build.py`")
+        fn = lib.texgs_sh_flush
+        fn.restype, fn.argtypes = SH_FLUSH_SIGNATURE
+        _sh_flush_fn = fn
+    return _sh_flush_fn
 
 
 def shard_views(num_views: int, rank: int, world: int) -> List[int]:
@@ -73,6 +103,109 @@ class GradBucket:
         self.replicas = []
         self.active = 0
         self.before_accumulate = None
+        # deferred SH gradient (begin_deferred): the mode, the pool of [N,3] residue buffers by (N, device), how many of each are
+        # handed out, and the views waiting for the flush -- (means3D leaf, shs leaf, the means3D and shs the kernels read, campos,
+        # sh_degree, residue); holding the tensors keeps their memory alive until the flush has been issued
+        self.deferred = False
+        self.deferred_early_flush = True
+        self._param_ids = frozenset(id(p) for p in self.params)
+        self.residue_pool_size = SH_FLUSH_MAX_VIEWS
+        self._residues = {}
+        self._residues_used = {}
+        self._pending_sh = []
+        self.sh_flushes = 0             # texgs_sh_flush launches so far
+
+    # ---- deferred SH gradient -------------------------------------------------------------------------------------------------
+    # K8 re-reads a Gaussian's 45 SH coefficients and read-modify-writes its 45 dL/dSH floats for every view, to add a rank-1
+    # product of 15 basis values and the 3 floats of dL/dvd.  Inside ViewPipeline.run the bucket is read only after the last view,
+    # so K8 stores those 3 floats (the "residue") and one texgs_sh_flush per step touches the rows once.
+
+    def begin_deferred(self, early_flush=True):
+        """Enter the deferred mode (ViewPipeline.run, at its start).  early_flush=False: a full residue pool grows instead of
+        flushing in the middle of the step (order="none": nothing orders a stream's flush against the other streams' K8)."""
+        assert not self._pending_sh, "begin_deferred with views pending: flush_deferred first"
+        self.deferred = True
+        self.deferred_early_flush = bool(early_flush)
+
+    def wants_deferred(self, means3D, shs):
+        """True when the backward of a view with these inputs should defer: the mode is on and BOTH tensors are sunk into the bucket"""
+        if not self.deferred or means3D is None or shs is None or means3D is shs:
+            return False
+        ids = self._param_ids
+        return id(means3D) in ids and id(shs) in ids and shs.dim() == 3 and shs.shape[1] >= 1
+
+    def deferred_pool_full(self, means3D):
+        key = (means3D.shape[0], means3D.device)
+        return self.deferred_early_flush and self._residues_used.get(key, 0) >= self.residue_pool_size
+
+    def sh_residue_for(self, leaf_means3D, leaf_shs, means3D, shs, campos, sh_degree):
+        """An [N,3] residue buffer for K8 (TexGSGrads.dL_dvd_residue) of one view, registered for the flush in call order.
+        `leaf_*`: the registered parameters (their slices are the flush's sinks); `means3D`, `shs`, `campos`: the contiguous
+        float32 tensors that view's kernels read.  The caller flushes first when deferred_pool_full() (at a point where its
+        stream is ordered after the earlier views' K8)."""
+        assert self.deferred, "sh_residue_for outside begin_deferred / flush_deferred"
+        key = (means3D.shape[0], means3D.device)
+        pool = self._residues.setdefault(key, [])
+        used = self._residues_used.get(key, 0)
+        if used == len(pool):
+            pool.append(torch.empty(means3D.shape[0], 3, dtype=torch.float32, device=means3D.device))
+        self._residues_used[key] = used + 1
+        res = pool[used]
+        self._pending_sh.append((leaf_means3D, leaf_shs, means3D, shs, campos, int(sh_degree), res))
+        return res
+
+    def _slice_of(self, tensor):
+        for p, (off, n) in zip(self.params, self.slices):
+            if p is tensor:
+                return self.flat[off:off + n]
+        raise KeyError("not a registered parameter")
+
+    def flush_pending(self):
+        """Issue texgs_sh_flush for the views registered so far, on the current stream, into `flat` (never a replica); the
+        residue buffers are free again afterwards (stream order protects them).  The mode stays as it is."""
+        pending, self._pending_sh = self._pending_sh, []
+        self._residues_used = {}
+        if not pending:
+            return
+        from . import _lib
+        fn = sh_flush_entry()
+        k = 0
+        while k < len(pending):
+            leaf_m, leaf_s, m3, shs = pending[k][:4]
+            same = lambda e: e[0] is leaf_m and e[1] is leaf_s and e[2].data_ptr() == m3.data_ptr() and e[3].data_ptr() == shs.data_ptr()
+            run = []
+            while k < len(pending) and len(run) < SH_FLUSH_MAX_VIEWS and same(pending[k]):
+                run.append(pending[k])
+                k += 1
+            recs = (ShFlushView * len(run))(*[ShFlushView(e[4].data_ptr(), e[6].data_ptr(), e[5], shs.shape[1]) for e in run])
+            with _lib.on(m3.device) as stream:
+                _lib.call(fn, m3.shape[0], shs.shape[1], m3.data_ptr(), shs.data_ptr(), self._slice_of(leaf_s).data_ptr(),
+                          self._slice_of(leaf_m).data_ptr(), recs, len(run), stream)
+            self.sh_flushes += 1
+
+    def flush_deferred(self):
+        """Leave the deferred mode (ViewPipeline.run, in its `finally`, after the streams are joined and the replicas folded):
+        whatever is pending is flushed on the current stream; afterwards .grad of shs and means3D is complete."""
+        try:
+            self.flush_pending()
+        finally:
+            self.deferred = False
+            self._pending_sh = []
+            self._residues_used = {}
+
+    def _assert_flushed(self, what, segment=None):
+        """Nothing may read or clear gradients that the flush has not completed.  `segment` = (offset, count): only that run of the flat
+        buffer is about to be read -- the texture segment is all-reduced from inside the last view's backward (texture_ready), with
+        every view's SH part still pending, and that is fine: the flush adds into the shs and means3D slices alone."""
+        if not self._pending_sh:
+            return
+        if segment is not None:
+            lo, hi = segment[0], segment[0] + segment[1]
+            slices = {id(p): sl for p, sl in zip(self.params, self.slices)}
+            touched = any(off < hi and lo < off + n for e in self._pending_sh for off, n in (slices[id(e[0])], slices[id(e[1])]))
+            if not touched:
+                return
+        raise AssertionError(f"GradBucket.{what} with deferred SH gradients pending: flush_deferred() first")
 
     def select(self, k: int):
         """Accumulate the following views into buffer k (0 = `flat`, the one .grad aliases; k > 0 = a private replica,
@@ -108,6 +241,7 @@ class GradBucket:
         return None
 
     def zero(self):
+        self._assert_flushed("zero")
         self.flat.zero_()
         for p, (off, n) in zip(self.params, self.slices):   # re-attach if something replaced .grad
             if p.grad is None or p.grad.data_ptr() != self.flat.data_ptr() + 4 * off:
@@ -135,6 +269,7 @@ class GradBucket:
         by the gradient's own running magnitude).  The fp32 buffer is converted into a staging tensor on the comm stream, reduced,
         and converted back in place."""
         off, n = segment if segment is not None else (0, self.flat.numel())
+        self._assert_flushed("all_reduce_async", (off, n))
         buf = self.flat[off:off + n]
         if dist.get_backend() != "nccl" or not self.flat.is_cuda:
             for ev in after:                    # (other streams' texture-gradient kernels: the host copy must see their sums)
@@ -169,6 +304,7 @@ class GradBucket:
 
     def wait(self):
         """Make the current stream wait for every all-reduce issued with all_reduce_async (before the optimizer / zero())."""
+        self._assert_flushed("wait")
         if getattr(self, "_pending", False):
             torch.cuda.current_stream(self.flat.device).wait_stream(self._comm)
             self._pending = False
@@ -204,6 +340,7 @@ class GradBucket:
 
         Backend "nccl" (= RCCL over xGMI) reduces the device buffer in place.  Any other backend (gloo: the CPU tests, and
         the single-GPU rehearsal where two ranks share one device -- RCCL refuses that) goes through a pinned host copy."""
+        self._assert_flushed("all_reduce")
         if dist.get_backend() == "nccl":
             dist.all_reduce(self.flat, op=dist.ReduceOp.SUM)
         else:
@@ -281,26 +418,37 @@ class ViewPipeline:
         "none"       -- nothing: every stream accumulates into its own replica of the bucket, folded at the end."""
         results = []
         views = list(views)
+        # the deferred SH gradient of a GradBucket (a sink without these two methods is driven exactly as before)
+        begin_deferred = getattr(sink, "begin_deferred", None) if backward_fn is not None else None
+        flush_deferred = getattr(sink, "flush_deferred", None) if begin_deferred is not None else None
         if not self.streams:                       # depth 1: the caller's stream, nothing to order
-            for i, v in enumerate(views):
-                obj = forward_fn(v)
-                if prefetch_fn is not None and i + 1 < len(views):
-                    prefetch_fn(views[i + 1])
-                if backward_fn is not None:
-                    if texture_ready is not None and sink is not None and i == len(views) - 1:
-                        sink.before_accumulate = lambda: texture_ready([])
-                    try:
-                        backward_fn(obj)
-                    finally:
-                        if sink is not None:
-                            sink.before_accumulate = None
-                results.append(obj)
+            if flush_deferred is not None:
+                begin_deferred()
+            try:
+                for i, v in enumerate(views):
+                    obj = forward_fn(v)
+                    if prefetch_fn is not None and i + 1 < len(views):
+                        prefetch_fn(views[i + 1])
+                    if backward_fn is not None:
+                        if texture_ready is not None and sink is not None and i == len(views) - 1:
+                            sink.before_accumulate = lambda: texture_ready([])
+                        try:
+                            backward_fn(obj)
+                        finally:
+                            if sink is not None:
+                                sink.before_accumulate = None
+                    results.append(obj)
+            finally:
+                if flush_deferred is not None:
+                    flush_deferred()
             return results
         if order not in ("backward", "accumulate", "none"):
             raise ValueError(order)
         if sink is None and order != "backward":
             order = "backward"
         cur = torch.cuda.current_stream(self.device)
+        if flush_deferred is not None:
+            begin_deferred(early_flush=order != "none")
         for s in self.streams:
             s.wait_stream(cur)
         prev_bwd = None
@@ -348,4 +496,6 @@ class ViewPipeline:
                 cur.wait_stream(s)
             if sink is not None and order == "none":
                 sink.fold()
+            if flush_deferred is not None:          # on the caller's stream, which has just been joined with every stream: no new wait
+                flush_deferred()
         return results

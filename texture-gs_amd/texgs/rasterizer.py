@@ -636,7 +636,7 @@ def _plan_outputs(N, K, textured, has_cov, has_coff, want, sinks, device):
 
 
 def backward_raw(s: _State, dL_dcolor, dL_ddepth, dL_dnorm, dL_dalpha, sinks=None, before_accumulate=None,
-                 want=_lib.WANT_ALL):
+                 want=_lib.WANT_ALL, defer_sh=None):
     """Run K7+K8.  Returns grads (means3D, means2D, shs, opacities, scales, rotations, uvs, texture).
 
     `want` (TEXGS_WANT_* bits): WANT_TEXTURE = dL/dtexture, WANT_GAUSSIANS = every per-Gaussian gradient.  What is not wanted
@@ -648,7 +648,11 @@ def backward_raw(s: _State, dL_dcolor, dL_ddepth, dL_dnorm, dL_dalpha, sinks=Non
     `sinks` (optional): dict name -> existing float32 gradient buffer of the input's shape.  K8 ADDS into the sink of
     every per-Gaussian output that has one (TexGSGrads.accumulate bit mask: fused multi-view accumulation, or a leaf's
     existing .grad) and writes the others into one fresh allocation; a texture sink is used the same way (dL_dtexture is
-    always accumulated into).  Outputs written into a sink come back as None."""
+    always accumulated into).  Outputs written into a sink come back as None.
+
+    `defer_sh` (optional): (bucket, means3D leaf, shs leaf) -- a texgs.multiview.GradBucket in its deferred mode whose slices are
+    the sinks of BOTH leaves.  K8 then leaves the view-dependent colour's chain to the bucket's flush: it gets a residue buffer from the bucket
+    (TexGSGrads.dL_dvd_residue), which registers this view's camera position and degree with it."""
     lib = _lib.load()
     if not s.tensors["for_backward"]:
         raise RuntimeError("this forward ran with for_backward=False (no survivor lists were kept): its backward cannot run")
@@ -695,13 +699,25 @@ def backward_raw(s: _State, dL_dcolor, dL_ddepth, dL_dnorm, dL_dalpha, sinks=Non
                            _ptr(outs.get("shs")), _ptr(outs.get("opacities")), _ptr(outs.get("scales")), _ptr(outs.get("rotations")),
                            _ptr(outs.get("uvs")), _ptr(d_tex), _ptr(outs.get("color_offset")), _ptr(outs.get("cov3D")), want,
                            _ptr(bins.rec) if bins else None, _ptr(bins.cursor) if bins else None,
-                           _ptr(bins.base) if bins else None, bins.cap if bins else 0, mask)
+                           _ptr(bins.base) if bins else None, bins.cap if bins else 0, mask, None)
         refs = [C.byref(x) for x in (s.frame, s.inputs, s.geom, s.bin, s.img, grads)]
-        if before_accumulate is None:
+        defer = defer_sh is not None and want_g and "shs" in outs and "means3D" in sinks and "shs" in sinks
+        if before_accumulate is None and not defer:
             _lib.call(lib.texgs_backward, *refs, stream)
         else:
             _lib.call(lib.texgs_backward_render, *refs, stream)
-            before_accumulate()
+            if before_accumulate is not None:
+                before_accumulate()
+            if defer:
+                # (here, not earlier: after before_accumulate this stream is ordered behind every earlier view's K8, which is what an
+                #  early flush of a full pool -- it reads their residues and adds into the sinks -- needs)
+                bucket, leaf_m, leaf_s = defer_sh
+                if bucket.deferred_pool_full(a.means3D):
+                    bucket.flush_pending()
+                campos = s.tensors["keep"][-1]           # (_make_frame appends bg, viewmatrix, projmatrix, campos last)
+                assert campos.data_ptr() == s.frame.campos
+                residue = bucket.sh_residue_for(leaf_m, leaf_s, a.means3D, a.shs, campos, s.frame.sh_degree)
+                grads.dL_dvd_residue = residue.data_ptr()
             _lib.call(lib.texgs_backward_preprocess, *refs[:3], refs[5], stream)
     if bins is not None:
         bins.after_call()
@@ -783,9 +799,12 @@ class _RasterizeGaussians(torch.autograd.Function):
             bucket = bool(sinks)
         if not bucket and DIRECT_LEAF_GRADS:
             sinks = {k: g for k, g in ((k, _leaf_grad_sink(v)) for k, v in ctx.named.items()) if g is not None}
+        wants_deferred = getattr(ctx.grad_sink, "wants_deferred", None) if bucket else None
+        defer = wants_deferred is not None and wants_deferred(ctx.named["means3D"], ctx.named["shs"])
         d_means3D, d_means2D, d_shs, d_op, d_scales, d_rot, d_uvs, d_tex = backward_raw(
             s, dL_dcolor, dL_ddepth, dL_dnorm, dL_dalpha, sinks=sinks or None,
-            before_accumulate=getattr(ctx.grad_sink, "before_accumulate", None) if bucket else None, want=ctx.want)
+            before_accumulate=getattr(ctx.grad_sink, "before_accumulate", None) if bucket else None, want=ctx.want,
+            defer_sh=(ctx.grad_sink, ctx.named["means3D"], ctx.named["shs"]) if defer else None)
         d_coff = s.tensors.get("d_color_offset")
         d_cov = s.tensors.get("d_cov3D")
         ctx.state = None
