@@ -558,6 +558,9 @@ k_render_fwd(PixArgs a, float* __restrict__ out_color, float* __restrict__ out_d
 //   stage C2 dense over TASKS = the items of one (iteration, quadrant) = up to 16 consecutive items of ONE Gaussian, four
 //            tasks per round (one per DPP row): the 28 per-Gaussian moment terms of every item, a 16-lane transposing butterfly
 //            (DPP only, wave_ops.h), and the 16 lanes add the Gaussian's 128-byte accumulator row as two 64-byte runs.
+// Order inside a chunk (render_bwd_body.h): front_a(n) [record gathers] -> C1(n - 1) -> front_b(n) [taps] -> C2(n - 1) -> A(n + 1) ->
+// back(n), which writes the items of segment n whole; C of the chunk's last segment at the chunk's end.  Stage C fills the waits of
+// the NEXT segment's gathers and taps with work that depends on neither (K7 570 -> 552 us, profiles/k7_segment_order_summary.txt).
 #define BWD_MAX_IT 16
 struct TexBinArgs {
     uint32_t* rec;         // [cap][4] 16-byte records (rec_pack); bin b owns [base[b], base[b+1])

@@ -8,7 +8,8 @@ typedef Planes PlanesT;
 #endif
 struct __attribute__((aligned(16))) BwdLds {      // bytes: configuration lds (BQ_CAP 128, planes in LDS) / occ (BQ_CAP 64, K7_GATHER)
     float4 items[BQ_CAP * 3 + 3];       // 6192 / 3120: 3 float4 per item {T -> w, s -> dL/dpower, alpha_raw, key} {dc, du0} {du1, du2, inv, dden}; + one all-zero item
-    float4 abuf[BQ_CAP];                // 2048 / 1024: {T, -, alpha_raw, key} of the NEXT segment's items (stage A runs one segment ahead of B / C)
+                                        //   written whole by stage B's back half: until then they are the PREVIOUS segment's, which stage C is still reading
+    float4 abuf[BQ_CAP];                // 2048 / 1024: {T, -, alpha_raw, key} of the NEXT segment's items (stage A runs one segment ahead of B, two ahead of C)
     PlanesT p;                          // 6768 / 2080
     float4 dpix[64];                    // 1024: dL/d(r, g, b, alpha) of the wave's pixels
     float4 dgeo[64];                    // 1024: dL/d(depth, normal)
@@ -125,6 +126,7 @@ k_render_bwd(PixArgs a, TexBinArgs tb, const float* __restrict__ final_T, const 
         uint32_t fxw, fyw;                                // the record's first word; cell + high fraction bits (rec_word0 / rec_pack)
         uint32_t o00, dox, doy;                           // tap byte offsets: o01 = o00 + dox, o10 = o00 + doy, o11 = o00 + dox + doy
         float w, vd0, vd1, vd2, nu0, nu1, nu2, inv;
+        float T, araw;                                    // GEO: the item's first word waits here for the back half (w is formed there)
         float fx, fy, ka, kb, kc, kd;                     // d(col,row)/d(ua,ub,m) factors of the cube projection
         Texel3 t00, t01, t10, t11;
 #if K7_GATHER
@@ -142,12 +144,12 @@ k_render_bwd(PixArgs a, TexBinArgs tb, const float* __restrict__ final_T, const 
         float4 it = make_float4(1.f, 0.f, 0.f, 0.f);
         if (R.have) {
             it = L.abuf[R.e];
-            if constexpr (GEO) L.items[R.e * 3] = it;         // (the previous segment's stage C has read its items by now)
-        }
+        }                                                     // (L.items still holds the previous segment: stage C reads it after this)
         R.key = __float_as_uint(it.w);
         R.pl = KEY_PL(R.key);
         R.jj = KEY_J(R.key);
-        R.w = fminf(TG_ALPHA_MAX, it.z) * it.x;
+        if constexpr (GEO) { R.T = it.x; R.araw = it.z; }
+        else R.w = fminf(TG_ALPHA_MAX, it.z) * it.x;
 #if K7_GATHER
         // the shading record of the item's Gaussian from global memory (an L2 hit; lanes of one task read the same 80 bytes)
         const float4* __restrict__ sp = a.rec_shade + (TEXGS_REC_SHADE_FLOATS / 4) * (size_t)(uint32_t)__builtin_amdgcn_ds_bpermute(R.jj << 2, (int)cid);
@@ -229,7 +231,8 @@ k_render_bwd(PixArgs a, TexBinArgs tb, const float* __restrict__ final_T, const 
     auto back = [&](Round& R) {
         float x0 = 0.f, x1 = 0.f, x2 = 0.f;
         if (R.have) {
-            const float w = R.w;
+            float w;
+            if constexpr (GEO) w = fminf(TG_ALPHA_MAX, R.araw) * R.T; else w = R.w;
             const float4 dp = L.dpix[R.pl];
             const float d0 = dp.x, d1 = dp.y, d2 = dp.z;
             // bilinear sample and its two derivatives in the nested form c = t00 + fx e + fy b, e = a + fy d = dc/dfx,
@@ -262,7 +265,7 @@ k_render_bwd(PixArgs a, TexBinArgs tb, const float* __restrict__ final_T, const 
                 const float4 c5 = L.p.C[R.jj];
 #endif
                 const float4 dg = L.dgeo[R.pl];
-                L.items[R.e * 3].y = qv + c5.x * dg.x + c5.y * dg.y + c5.z * dg.z + c5.w * dg.w + dp.w;
+                L.items[R.e * 3] = make_float4(R.T, qv + c5.x * dg.x + c5.y * dg.y + c5.z * dg.z + c5.w * dg.w + dp.w, R.araw, __uint_as_float(R.key));
                 float du0 = 0.f;
                 if constexpr (UVG) {
                     const float dLdcol = x0 * e0 + x1 * e1 + x2 * e2;
@@ -377,7 +380,7 @@ k_render_bwd(PixArgs a, TexBinArgs tb, const float* __restrict__ final_T, const 
                 ++t;
             }
         };
-        auto stage_c = [&](const Seg& sg) {
+        auto stage_c1 = [&](const Seg& sg) {
             // ================================================================ stage C1: per-pixel recurrence, iteration by iteration
             // dL/dalpha_i = T_i s_i - (B_i + T_final bg . dL/dcolour) / (1 - alpha_i),  B_i = sum over the contributors k BEHIND i
             // of s_k alpha_k T_k: one running sum per pixel (`behind`), back to front.  s_i (colour . dL/dcolour + geometry
@@ -398,6 +401,8 @@ k_render_bwd(PixArgs a, TexBinArgs tb, const float* __restrict__ final_T, const 
                     *reinterpret_cast<float2*>(&L.items[it * 3]) = make_float2(w, araw * dL_dalpha_);
                 }
             }
+        };
+        auto stage_c2 = [&](const Seg& sg) {
             // ================================================================ stage C2: per-Gaussian moment sums, 16 lanes per task
             // task list: lane (k, q) = (iteration k, quadrant q) of the segment looks at its row of the iteration's ballot
             int ntask;
@@ -483,9 +488,15 @@ k_render_bwd(PixArgs a, TexBinArgs tb, const float* __restrict__ final_T, const 
         // in-order vmcnt the back half waits on counts nothing that was issued in between.  (Scheduling barriers: left alone, the
         // machine scheduler interleaved both back halves and waited for all eight taps first.)  No look-ahead across chunks: the
         // next chunk's planes are not in LDS yet.
+        // Stage C runs ONE SEGMENT LATE, inside the same waits: C1(n - 1), LDS only, between the record gathers of front_a(n) and
+        // front_b(n), which needs them; C2(n - 1) behind the taps of front_b(n).  It depends on nothing segment n has in flight, and
+        // L.items is its own until back(n) writes the items of segment n whole.  A(n + 1) comes after C2: the in-order vmcnt that
+        // back(n) waits on counts C2's accumulator atomics as well, and stage A's span is the time they have to be acknowledged.
+        // C of a chunk's last segment runs at the end of the chunk (it reads this chunk's plane A and ids).
         constexpr int NR = (BQ_CAP + 63) / 64;          // rounds of 64 items per segment, all of them in flight together
         static_assert(BQ_CAP <= 192, "item indices travel in 8 bits (task words), and index BQ_CAP is the all-zero item");
-        Seg nxt;
+        Seg nxt, prv;
+        prv.n_items = 0; prv.n_it = 0; prv.it_lo = 0u; prv.it_hi = 0u; prv.it_first = 0u;
         stage_a(nxt);
         while (nxt.n_items > 0) {
             const Seg cur = nxt;
@@ -497,6 +508,10 @@ k_render_bwd(PixArgs a, TexBinArgs tb, const float* __restrict__ final_T, const 
             for (int r = 0; r < NR; ++r)
                 if (r == 0 || r * 64 < cur.n_items) front_a(r * 64, R[r], cur.n_items);
             __builtin_amdgcn_sched_barrier(0);
+            if constexpr (GEO) {
+                stage_c1(prv);                          // (no iterations in a chunk's first segment)
+                __builtin_amdgcn_sched_barrier(0);
+            }
 #pragma unroll
             for (int r = 0; r < NR; ++r)
                 if (r == 0 || r * 64 < cur.n_items) front_b(R[r]);
@@ -504,12 +519,18 @@ k_render_bwd(PixArgs a, TexBinArgs tb, const float* __restrict__ final_T, const 
 #pragma unroll
             for (int r = 0; r < NR; ++r)
                 if (r == 0 || r * 64 < cur.n_items) { front_a(r * 64, R[r], cur.n_items); front_b(R[r]); }
+            static_assert(!GEO, "stage C has its place in the segment order of the K7_GATHER configuration only");
 #endif
             __builtin_amdgcn_sched_barrier(0);
+            if constexpr (GEO) {
+                if (prv.n_it > 0) stage_c2(prv);
+                __builtin_amdgcn_sched_barrier(0);
+            }
             nxt.n_items = 0; nxt.n_it = 0;
             if (t < tmax) {
                 stage_a(nxt);
             }
+            if constexpr (GEO) __builtin_amdgcn_wave_barrier();      // (C(n - 1) has read L.items: back(n) may write them)
             // ================================================================ stage B, back halves
 #pragma unroll
             for (int r = 0; r < NR; ++r) {
@@ -517,7 +538,11 @@ k_render_bwd(PixArgs a, TexBinArgs tb, const float* __restrict__ final_T, const 
                 if (r == 0 || r * 64 < cur.n_items) back(R[r]);
             }
             __builtin_amdgcn_wave_barrier();
-            if constexpr (GEO) stage_c(cur);
+            if constexpr (GEO) prv = cur;
+        }
+        if constexpr (GEO) {
+            // the chunk's last segment: the next chunk overwrites plane A and the ids stage C2 reads
+            if (prv.n_it > 0) { stage_c1(prv); stage_c2(prv); }
             __builtin_amdgcn_wave_barrier();
         }
     }
