@@ -36,21 +36,22 @@ UNITS = {
     "density.hip": ["-ffp-contract=off"],     # the per-step statistics are a bit-exact contract: x*x + y*y with separate roundings
     "metrics.hip": ["-ffp-contract=off"],     # fp64 sums of exact fp32 products, reproducible against numpy: no fused multiply-add
     "optim.hip": ["-ffp-contract=off"],       # the Adam step's arithmetic is a bit-exact contract: one rounding per operation
+    "mlp.hip": [],
     "abi.hip": [],
 }
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "wave_ops.h"), os.path.join(CSRC, "render_bwd_body.h"),
            os.path.join(ROOT, "include", "texgs.h"), os.path.join(ROOT, "include", "texgs_optim.h"),
-           os.path.join(ROOT, "include", "texgs_multiview.h")]
+           os.path.join(ROOT, "include", "texgs_multiview.h"), os.path.join(ROOT, "include", "texgs_mlp.h")]
 
 
 def build_id():
-    """Identity of what libtexgs.so is built FROM: sha256 over csrc/*, the three headers of include/ and the compile flags (16 hex digits).
+    """Identity of what libtexgs.so is built FROM: sha256 over csrc/*, the headers of include/ and the compile flags (16 hex digits).
     build() bakes it into the library (texgs_build_id()); texgs/_lib.py recomputes it from the tree and refuses a library that
     was built from other sources -- the prebuilt .so is what travels to the GPU box, mtimes do not."""
     import hashlib
     h = hashlib.sha256()
     files = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))) \
-        + [os.path.join(ROOT, "include", f) for f in ("texgs.h", "texgs_optim.h", "texgs_multiview.h")]
+        + [os.path.join(ROOT, "include", f) for f in ("texgs.h", "texgs_optim.h", "texgs_multiview.h", "texgs_mlp.h")]
     for f in files:
         h.update(os.path.basename(f).encode())
         h.update(open(f, "rb").read())

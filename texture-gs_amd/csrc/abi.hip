@@ -586,6 +586,54 @@ int texgs_sh_flush(int32_t N, int32_t K, const float* means3D, const float* shs,
     return launched("sh_flush", launch_sh_flush(N, K, means3D, shs, dL_dshs, dL_dmeans3D, views, count, s), s, false);
 }
 
+// include/texgs_mlp.h: the shape, by name
+static int check_mlp(const TexGSMlp* m) {
+    if (!m) return fail_msg("mlp is NULL");
+    const char* what = nullptr;
+    int v = 0;
+    if (m->n_neurons != TEXGS_MLP_WIDTH) { what = "n_neurons must be 128"; v = m->n_neurons; }
+    else if (m->n_hidden_layers < 1 || m->n_hidden_layers > TEXGS_MLP_MAX_HIDDEN_LAYERS) { what = "n_hidden_layers must be 1 or 2"; v = m->n_hidden_layers; }
+    else if (m->n_in < 1 || m->n_in > TEXGS_MLP_WIDTH) { what = "n_in must be in [1,128]"; v = m->n_in; }
+    else if (m->n_out < 1 || m->n_out > TEXGS_MLP_WIDTH) { what = "n_out must be in [1,128]"; v = m->n_out; }
+    if (!what) return 0;
+    snprintf(g_err, sizeof(g_err), "the fused MLP does not support this shape: %s, got %d", what, v);
+    return -1;
+}
+
+static int check_mlp_call(const TexGSMlp* m, int32_t N, const void* params, const void* temp) {
+    if (int r = check_mlp(m)) return r;
+    if (N < 0) return fail_msg("N < 0");
+    if (N > INT32_MAX - TEXGS_MLP_FORWARD_TILE) return fail_msg("N too large: the tile count is a 32-bit integer");
+    if (!params || !temp) return fail_msg("NULL argument (params or temp)");
+    if ((uintptr_t)params & 3) return fail_msg("params must be 4-byte aligned");
+    if ((uintptr_t)temp & 15) return fail_msg("temp must be 16-byte aligned");
+    return 0;
+}
+
+size_t texgs_mlp_param_count(const TexGSMlp* mlp) { return check_mlp(mlp) ? 0 : mlp_param_count(mlp); }
+
+size_t texgs_mlp_forward_temp_bytes(const TexGSMlp* mlp, int32_t N) { return check_mlp(mlp) || N < 0 ? 0 : mlp_forward_temp_bytes(); }
+
+size_t texgs_mlp_backward_temp_bytes(const TexGSMlp* mlp, int32_t N) { return check_mlp(mlp) || N < 0 ? 0 : mlp_backward_temp_bytes(N); }
+
+int texgs_mlp_forward(const TexGSMlp* mlp, const float* params, const float* x, int32_t N, float* y, void* temp, void* stream) {
+    if (int r = check_mlp_call(mlp, N, params, temp)) return r;
+    if (N == 0) return 0;
+    if (!x || !y) return fail_msg("NULL argument (x or y)");
+    if (((uintptr_t)x | (uintptr_t)y) & 3) return fail_msg("x and y must be 4-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    return launched("mlp_forward", launch_mlp_forward(mlp, params, x, N, y, temp, s), s, false);
+}
+
+int texgs_mlp_backward(const TexGSMlp* mlp, const float* params, const float* x, const float* dy, int32_t N, float* dx, float* d_params,
+                       void* temp, void* stream) {
+    if (int r = check_mlp_call(mlp, N, params, temp)) return r;
+    if (N > 0 && (!x || !dy)) return fail_msg("NULL argument (x or dy)");
+    if (((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx | (uintptr_t)d_params) & 3) return fail_msg("x, dy, dx and d_params must be 4-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    return launched("mlp_backward", launch_mlp_backward(mlp, params, x, dy, N, dx, d_params, temp, s), s, false);
+}
+
 int texgs_selftest_waveops(const float* seed128, float* out576, void* stream) {
     if (!seed128 || !out576) return fail_msg("NULL argument");
     return launched("selftest_waveops", launch_selftest_waveops(seed128, out576, (hipStream_t)stream), (hipStream_t)stream, false);

@@ -5,6 +5,7 @@
 #include "texgs.h"
 #include "texgs_optim.h"
 #include "texgs_multiview.h"
+#include "texgs_mlp.h"
 
 // ---- operator constants (restated in oracle/texgs_torch.py) ----
 #define TG_NEAR_Z        0.2f
@@ -128,3 +129,9 @@ size_t eval_metrics_temp_bytes(int H, int W);
 hipError_t launch_eval_metrics(const float* image, const float* gt_image, const float* norm, const float* gt_norm, const float* alpha, int H,
                         int W, int clamp01, void* temp, double* row, hipStream_t s);
 hipError_t launch_adam_step(const TexGSAdamTensor* tensors, int count, int zero_grads, hipStream_t s);
+size_t mlp_param_count(const TexGSMlp* m);      // the shape is validated by the caller (abi.hip check_mlp)
+size_t mlp_forward_temp_bytes();
+size_t mlp_backward_temp_bytes(int N);
+hipError_t launch_mlp_forward(const TexGSMlp* m, const float* params, const float* x, int N, float* y, void* temp, hipStream_t s);
+hipError_t launch_mlp_backward(const TexGSMlp* m, const float* params, const float* x, const float* dy, int N, float* dx, float* d_params,
+                               void* temp, hipStream_t s);
