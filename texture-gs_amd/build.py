@@ -3,7 +3,7 @@
 Objects are rebuilt only when their sources are newer.  preprocess.hip is built with -ffp-contract=off (its
 fp32 operation order is part of the bit-exact key/rect/radius contract) and so is points.hip (its squared distance is
 compared bit for bit), density.hip (its per-step statistics likewise), optim.hip (the Adam step's arithmetic likewise) and
-metrics.hip (its fp64 sums are compared with numpy's);
+metrics.hip (its fp64 sums are compared with numpy's) and present.hip (its output bytes and floats are compared bit for bit);
 the render kernels allow contraction
 and use hardware fp32 atomics (-munsafe-fp-atomics).
 """
@@ -37,11 +37,13 @@ UNITS = {
     "metrics.hip": ["-ffp-contract=off"],     # fp64 sums of exact fp32 products, reproducible against numpy: no fused multiply-add
     "optim.hip": ["-ffp-contract=off"],       # the Adam step's arithmetic is a bit-exact contract: one rounding per operation
     "mlp.hip": [],
+    "present.hip": ["-ffp-contract=off"],     # its bytes and floats are a bit-exact contract: one rounding per operation, no fused multiply-add
     "abi.hip": [],
 }
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "wave_ops.h"), os.path.join(CSRC, "render_bwd_body.h"),
            os.path.join(ROOT, "include", "texgs.h"), os.path.join(ROOT, "include", "texgs_optim.h"),
-           os.path.join(ROOT, "include", "texgs_multiview.h"), os.path.join(ROOT, "include", "texgs_mlp.h")]
+           os.path.join(ROOT, "include", "texgs_multiview.h"), os.path.join(ROOT, "include", "texgs_mlp.h"),
+           os.path.join(ROOT, "include", "texgs_present.h")]
 
 
 def build_id():
@@ -51,7 +53,7 @@ def build_id():
     import hashlib
     h = hashlib.sha256()
     files = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))) \
-        + [os.path.join(ROOT, "include", f) for f in ("texgs.h", "texgs_optim.h", "texgs_multiview.h", "texgs_mlp.h")]
+        + [os.path.join(ROOT, "include", f) for f in ("texgs.h", "texgs_optim.h", "texgs_multiview.h", "texgs_mlp.h", "texgs_present.h")]
     for f in files:
         h.update(os.path.basename(f).encode())
         h.update(open(f, "rb").read())

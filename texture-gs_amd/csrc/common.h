@@ -6,6 +6,7 @@
 #include "texgs_optim.h"
 #include "texgs_multiview.h"
 #include "texgs_mlp.h"
+#include "texgs_present.h"
 
 // ---- operator constants (restated in oracle/texgs_torch.py) ----
 #define TG_NEAR_Z        0.2f
@@ -135,3 +136,7 @@ size_t mlp_backward_temp_bytes(int N);
 hipError_t launch_mlp_forward(const TexGSMlp* m, const float* params, const float* x, int N, float* y, void* temp, hipStream_t s);
 hipError_t launch_mlp_backward(const TexGSMlp* m, const float* params, const float* x, const float* dy, int N, float* dx, float* d_params,
                                void* temp, hipStream_t s);
+size_t depth_colour_temp_bytes(int H, int W);      // the arguments of these three are validated by the caller (abi.hip)
+hipError_t launch_present(const TexGSPresent* p, hipStream_t s);
+hipError_t launch_depth_colour(const TexGSDepthColour* d, void* temp, hipStream_t s);
+hipError_t launch_cube_cross(const TexGSCubeCross* c, hipStream_t s);

@@ -8,7 +8,8 @@ skimage.metrics.structural_similarity(channel_axis=0, data_range=1.0) -- uniform
 -- NOT the training loss of texgs.losses (11x11 Gaussian window, zero padding, population covariance).  Images are float32 [3,H,W]
 with H, W >= 7 (the window has to fit; skimage raises too), contiguous, on the GPU: there is no CPU fallback.
 
-Not here: LPIPS (its network weights are not part of this project) and the JET depth colour map of train.py:22-37."""
+Not here: LPIPS (its network weights are not part of this project).  The depth picture of train.py:22-37 is texgs.present.depth_colour;
+OpenCV's own JET table comes in through its `lut=` argument."""
 import numpy as np
 import torch
 
