@@ -7,6 +7,7 @@
 #include "texgs_multiview.h"
 #include "texgs_mlp.h"
 #include "texgs_present.h"
+#include "texgs_ingest.h"
 
 // ---- operator constants (restated in oracle/texgs_torch.py) ----
 #define TG_NEAR_Z        0.2f
@@ -140,3 +141,8 @@ size_t depth_colour_temp_bytes(int H, int W);      // the arguments of these thr
 hipError_t launch_present(const TexGSPresent* p, hipStream_t s);
 hipError_t launch_depth_colour(const TexGSDepthColour* d, void* temp, hipStream_t s);
 hipError_t launch_cube_cross(const TexGSCubeCross* c, hipStream_t s);
+int ingest_ksize(int inS, int outS, int filter);     // the arguments of these are validated by the caller (abi.hip)
+hipError_t launch_resize_taps(int inS, int outS, int filter, int32_t* taps, int32_t* bounds, hipStream_t s);
+size_t resize_temp_bytes(int H, int W, int C, int h, int w, int filter);
+hipError_t launch_resize_u8(const TexGSResize* r, void* temp, hipStream_t s);
+hipError_t launch_rgba_composite(const uint8_t* rgba, uint8_t* out, int H, int W, double bg0, double bg1, double bg2, hipStream_t s);
