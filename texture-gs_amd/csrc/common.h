@@ -8,6 +8,7 @@
 #include "texgs_mlp.h"
 #include "texgs_present.h"
 #include "texgs_ingest.h"
+#include "texgs_surface.h"
 
 // ---- operator constants (restated in oracle/texgs_torch.py) ----
 #define TG_NEAR_Z        0.2f
@@ -146,3 +147,6 @@ hipError_t launch_resize_taps(int inS, int outS, int filter, int32_t* taps, int3
 size_t resize_temp_bytes(int H, int W, int C, int h, int w, int filter);
 hipError_t launch_resize_u8(const TexGSResize* r, void* temp, hipStream_t s);
 hipError_t launch_rgba_composite(const uint8_t* rgba, uint8_t* out, int H, int W, double bg0, double bg1, double bg2, hipStream_t s);
+size_t surface_temp_bytes(int H, int W);             // the arguments of these are validated by the caller (abi.hip)
+hipError_t launch_surface_points(const TexGSSurfacePoints* p, void* temp, hipStream_t s);
+hipError_t launch_surface_compose(const TexGSSurfaceCompose* c, hipStream_t s);

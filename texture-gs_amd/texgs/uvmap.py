@@ -325,7 +325,8 @@ class UVMapLossCfg:
     lambda_inverse2: float = 1.0
 
 
-def uv_map_loss(depth, alpha, full_proj_transform, znear, zfar, uv_net, inv_uv_net, geo_emb, pcd, cfg=None, generator=None):
+def uv_map_loss(depth, alpha, full_proj_transform, znear, zfar, uv_net, inv_uv_net, geo_emb, pcd, cfg=None, generator=None,
+                world_xyz=None):
     """One stage-2 loss, term for term with models/uv_map_gaussian3d.py:167-232 (without the render and loss.backward()).
 
     depth, alpha: the untextured render [1, H, W] (or [H, W]) of the frozen Gaussians; full_proj_transform, znear, zfar: its
@@ -333,16 +334,27 @@ def uv_map_loss(depth, alpha, full_proj_transform, znear, zfar, uv_net, inv_uv_n
     inv_uv_net: InvUVNet; geo_emb: nn.Embedding(1, 128) or a [128] tensor; pcd [Q, 3]: the target point cloud; cfg: UVMapLossCfg,
     a dict or any object with the lambda_* attributes.  Returns (loss, stats).
 
+    world_xyz (opt-in): f32 [M, 3], the surface points of this render, e.g. `texgs.surface.surface_points(...).xyz`.  When given,
+    these rows are used instead of the torch unprojection and selection of uv_map_gaussian3d.py:180-183 (depth, alpha and the
+    camera are then not read); the default path is unchanged.
+
     Deviation: the reference's Linv2 branch calls `sample(depth.device)` (:223), passing the device as the point count; that
     line only runs with chamfer off.  Here it samples n_sample_points points."""
     cfg = UVMapLossCfg() if cfg is None else cfg
     lam = (lambda k: float(cfg.get(k, 0.0) or 0.0)) if isinstance(cfg, dict) else (lambda k: float(getattr(cfg, k, 0.0) or 0.0))
     emb = _emb_vector(geo_emb)
     dev = depth.device
-    d = depth.reshape(depth.shape[-2], depth.shape[-1])
-    world_xyz = depth2world(d, full_proj_transform, zfar, znear)
-    valid = alpha.reshape(-1) > 0.5
-    world_xyz = world_xyz.reshape(-1, 3)[valid].contiguous().detach()
+    if world_xyz is None:
+        d = depth.reshape(depth.shape[-2], depth.shape[-1])
+        world_xyz = depth2world(d, full_proj_transform, zfar, znear)
+        valid = alpha.reshape(-1) > 0.5
+        world_xyz = world_xyz.reshape(-1, 3)[valid].contiguous().detach()
+    else:
+        if not torch.is_tensor(world_xyz):
+            raise TypeError(f"world_xyz must be a torch.Tensor, got {type(world_xyz).__name__}")
+        if world_xyz.dim() != 2 or world_xyz.shape[1] != 3 or world_xyz.dtype != torch.float32:
+            raise ValueError(f"world_xyz must be float32 [M, 3], got {world_xyz.dtype} {tuple(world_xyz.shape)}")
+        world_xyz = world_xyz.contiguous().detach()
     uv, _ = uv_net.uvs_and_jacobian_with_grad(world_xyz, emb)
 
     loss = torch.zeros((), dtype=torch.float32, device=dev)
