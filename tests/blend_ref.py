@@ -36,8 +36,75 @@ UV_SLOTS = slice(PR.M_DEN, PR.M_VD)       # M_DEN, M_DN, M_PHI: the slots an unt
 IMAGES = ("color", "depth", "norm", "alpha", "final_T")
 
 
+class Windows:
+    """A texture of nominal resolution R of which only one window per face exists: face f owns the texels [y0, y0 + h) x [x0, x0 + w),
+    a dense [h, w, 3] block.  The blocks live one behind the other in `data` [sum h w, 3] (the autograd leaf); whatever blend() returns
+    per texel (d_tex, d_tex_abs, d_tex_ext, d_tex_x [sum h w, 3], d_tex_n [sum h w]) has that shape, and face() cuts one window out of
+    it.  index() turns (face, row, column) into rows of `data`; a tap that the caller needs and that lies outside its face's window
+    is an assertion failure, never a silent zero."""
+
+    def __init__(self, R, origins, blocks):
+        self.R = int(R)
+        self.y0, self.x0 = torch.tensor([int(o[0]) for o in origins]), torch.tensor([int(o[1]) for o in origins])
+        self.h, self.w = torch.tensor([int(b.shape[0]) for b in blocks]), torch.tensor([int(b.shape[1]) for b in blocks])
+        assert len(blocks) == 6 and all(b.dim() == 3 and b.shape[2] == 3 for b in blocks)
+        self.off = torch.cumsum(self.h * self.w, 0) - self.h * self.w
+        self.data = torch.cat([b.reshape(-1, 3) for b in blocks], 0).contiguous()
+
+    def _like(self, data):
+        o = Windows.__new__(Windows)
+        o.__dict__.update(self.__dict__)
+        o.data = data
+        return o
+
+    def to(self, dtype):
+        return self._like(self.data.to(dtype))
+
+    def clone(self):
+        return self._like(self.data.clone())
+
+    def requires_grad_(self, flag=True):
+        self.data.requires_grad_(flag)
+        return self
+
+    def shifted(self, face, dy, dx):
+        """the same blocks, the window of `face` moved by (dy, dx) texels: every tap of that face reads a neighbour's value"""
+        o = self._like(self.data)
+        o.y0, o.x0 = self.y0.clone(), self.x0.clone()
+        o.y0[face] += dy
+        o.x0[face] += dx
+        return o
+
+    def index(self, face, yy, xx, need):
+        ly, lx = yy - self.y0[face], xx - self.x0[face]
+        inside = (ly >= 0) & (ly < self.h[face]) & (lx >= 0) & (lx < self.w[face])
+        assert bool(inside[need].all()), ("a tap outside its face's window", int((need & ~inside).sum()))
+        z = torch.zeros_like(ly)
+        return self.off[face] + torch.where(inside, ly, z) * self.w[face] + torch.where(inside, lx, z)      # (an unneeded tap: the window's first texel, weight 0)
+
+    def face(self, per_texel, f):
+        """window f of a per-texel tensor shaped like `data` -> [h, w, ...]"""
+        o, h, w = int(self.off[f]), int(self.h[f]), int(self.w[f])
+        return per_texel[o:o + h * w].reshape(h, w, *per_texel.shape[1:])
+
+    @staticmethod
+    def of(texture, origins, sizes):
+        """the windows [y0, y0 + h) x [x0, x0 + w) of a dense [6,R,R,3] texture"""
+        return Windows(texture.shape[1], origins, [texture[f, y:y + h, x:x + w] for f, ((y, x), (h, w)) in enumerate(zip(origins, sizes))])
+
+
+def _texels(texture):
+    """the tensor that holds a texture's values: the [6,R,R,3] tensor itself, or a Windows' data"""
+    return texture.data if isinstance(texture, Windows) else texture
+
+
+def _tap_index(texture, face, yy, xx, need):
+    """the index of taps (face, yy, xx) into _texels(texture) and into everything shaped like it; need: the pairs whose tap is read"""
+    return (texture.index(face, yy, xx, need),) if isinstance(texture, Windows) else (face, yy, xx)
+
+
 class Case:
-    """rec [N,24] f32; point_list int64 [D]; ranges int64 [T,2]; texture f32 [6,R,R,3] or None; bg f32 [3]; up: the four upstream
+    """rec [N,24] f32; point_list int64 [D]; ranges int64 [T,2]; texture f32 [6,R,R,3], a Windows or None; bg f32 [3]; up: the four upstream
     gradients (f32, [3,H,W] / [1,H,W]); counters: the reached-edge counters of the builder."""
 
     def __init__(self, name, W, H, rec, point_list, ranges, texture, seed):
@@ -57,7 +124,7 @@ class Case:
 
     @property
     def R(self):
-        return 4 if self.texture is None else self.texture.shape[1]
+        return 4 if self.texture is None else (self.texture.R if isinstance(self.texture, Windows) else self.texture.shape[1])
 
     def in_lists(self):
         m = torch.zeros(self.N, dtype=torch.bool)
@@ -132,7 +199,7 @@ def _tile_forward(case, tile, rec, texture, dtype):
     t.Tfin = Tc[:, -1] if K else torch.ones(P, dtype=dtype)
     t.dpx, t.dpy = -t.dx, -t.dy                                            # dp = pixel - xy
     if texture is not None:
-        R = texture.shape[1]
+        R = case.R
         t.den = 1.0 + r[None, :, 6] * t.dpx + r[None, :, 7] * t.dpy
         G = r[:, 8:14].reshape(K, 3, 2)
         t.num = G[None, :, :, 0] * t.dpx[..., None] + G[None, :, :, 1] * t.dpy[..., None]
@@ -150,7 +217,9 @@ def _tile_forward(case, tile, rec, texture, dtype):
         cl = lambda v: v.clamp(0, R - 1)
         t.taps = [(cl(t.y0), cl(t.x0), (1 - t.fx) * (1 - t.fy)), (cl(t.y0), cl(t.x0 + 1), t.fx * (1 - t.fy)),
                   (cl(t.y0 + 1), cl(t.x0), (1 - t.fx) * t.fy), (cl(t.y0 + 1), cl(t.x0 + 1), t.fx * t.fy)]
-        t.tex = sum(wt[..., None] * texture[t.face, yy, xx] for yy, xx, wt in t.taps)
+        # the taps a result depends on: those of the contributing pairs (no other pair has a weight in any image or gradient)
+        t.tap_idx = [_tap_index(texture, t.face, yy, xx, t.contrib) for yy, xx, _ in t.taps]
+        t.tex = sum(wt[..., None] * _texels(texture)[ix] for ix, (_, _, wt) in zip(t.tap_idx, t.taps))
         t.colarg = SH_C0 * t.tex + r[None, :, 17:20] + 0.5
     else:
         t.colarg = (r[None, :, 17:20] + 0.5).expand(P, K, 3) + torch.zeros(P, K, 3, dtype=dtype)
@@ -191,7 +260,8 @@ def blend(case, dtype=F64, want_grads=True, colour_only=False, bg=None):
     sums of |terms| of each image, pairs [H,W] the contributors per pixel, block_contrib [T,4] the Gaussians that contribute to each
     8x8 block; with want_grads: M / M_abs [N,32], M_n [N] (contributing pairs of the Gaussian), d_rec [N,24] (autograd on the record
     leaf), M_ext [N,32] (the constants above: sum|terms| weighted with the roundings each term carries), d_tex / d_tex_abs / d_tex_ext [6,R,R,3], d_tex_n [6,R,R] and d_tex_x [6,R,R,3], the sum of |dL/d(texture sample)| of the footprints
-    that touch the texel whatever their tap weight (None without a texture).  colour_only: only dL/dcolour is non-zero."""
+    that touch the texel whatever their tap weight (None without a texture; window-shaped, see Windows, where the texture is one).
+    colour_only: only dL/dcolour is non-zero."""
     H, W, N = case.H, case.W, case.N
     if bg is not None:
         case = _with(case, bg=bg)
@@ -206,8 +276,9 @@ def blend(case, dtype=F64, want_grads=True, colour_only=False, bg=None):
         o.M, o.M_abs, o.M_n = torch.zeros(N, ACC, dtype=dtype), torch.zeros(N, ACC, dtype=dtype), torch.zeros(N, dtype=torch.int64)
         o.M_ext = torch.zeros(N, ACC, dtype=dtype)
         if texture is not None:
-            o.d_tex_abs, o.d_tex_n = torch.zeros_like(texture), torch.zeros(texture.shape[:3], dtype=torch.int64)
-            o.d_tex_x, o.d_tex_ext = torch.zeros_like(texture), torch.zeros_like(texture)
+            tv = _texels(texture)
+            o.d_tex_abs, o.d_tex_n = torch.zeros_like(tv), torch.zeros(tv.shape[:-1], dtype=torch.int64)
+            o.d_tex_x, o.d_tex_ext = torch.zeros_like(tv), torch.zeros_like(tv)
     up = {k: (v.to(dtype) if (k == "color" or not colour_only) else torch.zeros_like(v, dtype=dtype)) for k, v in case.up.items()}
     for tile in range(case.gx * case.gy):
         t = _tile_forward(case, tile, rec, texture, dtype)
@@ -252,15 +323,16 @@ def blend(case, dtype=F64, want_grads=True, colour_only=False, bg=None):
             o.M_n.index_add_(0, t.ids, t.contrib.sum(0))
             if texture is not None:
                 cm = t.contrib
-                for yy, xx, wt in t.taps:
-                    o.d_tex_abs.index_put_((t.face[cm], yy[cm], xx[cm]), (wt[cm][:, None] * t.tex.grad[cm]).abs(), accumulate=True)
-                    o.d_tex_n.index_put_((t.face[cm], yy[cm], xx[cm]), torch.ones(int(cm.sum()), dtype=torch.int64), accumulate=True)
-                    o.d_tex_x.index_put_((t.face[cm], yy[cm], xx[cm]), t.tex.grad[cm].abs(), accumulate=True)
-                    o.d_tex_ext.index_put_((t.face[cm], yy[cm], xx[cm]),
+                for ix, (yy, xx, wt) in zip(t.tap_idx, t.taps):
+                    ix = tuple(i[cm] for i in ix)
+                    o.d_tex_abs.index_put_(ix, (wt[cm][:, None] * t.tex.grad[cm]).abs(), accumulate=True)
+                    o.d_tex_n.index_put_(ix, torch.ones(int(cm.sum()), dtype=torch.int64), accumulate=True)
+                    o.d_tex_x.index_put_(ix, t.tex.grad[cm].abs(), accumulate=True)
+                    o.d_tex_ext.index_put_(ix,
                                            (wt[cm][:, None] * t.tex.grad[cm]).abs() * (depth.expand_as(wt)[cm] + PAIR_ROUNDINGS)[:, None], accumulate=True)
     if want_grads:
         o.d_rec = rec.grad.detach() if rec.grad is not None else torch.zeros(N, REC, dtype=dtype)
-        o.d_tex = None if texture is None else (texture.grad.detach() if texture.grad is not None else torch.zeros_like(texture))
+        o.d_tex = None if texture is None else (_texels(texture).grad.detach() if _texels(texture).grad is not None else torch.zeros_like(_texels(texture)))
         if texture is None:
             o.d_tex_abs = o.d_tex_n = o.d_tex_x = o.d_tex_ext = None
     return o
@@ -384,9 +456,10 @@ def decision_gaps(case):
     return worst, off, cnt
 
 
-def settle(case, seed, tries=40):
+def settle(case, seed, tries=40, phi_nudge=3e-3):
     """Nudge the Gaussians that own a pair within its bar of a threshold (opacity down by a few 2^-10, phi / viewdep / g by a few
-    1e-3) until none is left; the values stay float32.  Asserts that every gap holds: nothing is excused at comparison time."""
+    1e-3; phi_nudge: the large-R cases move phi by a hundredth of a texel instead, 3e-3 is five texels at R = 7168) until none is
+    left; the values stay float32.  Asserts that every gap holds: nothing is excused at comparison time."""
     g = torch.Generator().manual_seed(seed)
     for _ in range(tries):
         worst, off, cnt = decision_gaps(case)
@@ -396,7 +469,7 @@ def settle(case, seed, tries=40):
         r = case.rec
         r[off, 5] = (r[off, 5] * (1.0 - 2.0 ** -10 * (1.0 + 3.0 * torch.rand(n, generator=g)))).to(F32)
         if case.texture is not None:
-            r[off, 14:17] += 3e-3 * (torch.rand(n, 3, generator=g) - 0.5)
+            r[off, 14:17] += phi_nudge * (torch.rand(n, 3, generator=g) - 0.5)
             r[off, 6:8] *= 1.0 + 4e-3 * (torch.rand(n, 2, generator=g) - 0.5)
         r[off, 17:20] += 4e-3 * (torch.rand(n, 3, generator=g) - 0.5)
     assert not bool(off.any()), (case.name, "gaps", worst, int(off.sum()))
@@ -786,6 +859,109 @@ def build_uv_320():
     return case
 
 
+BIG_RESOLUTIONS = [2368, 5462, 7168]
+BIG_WINDOW = 96
+BIG_ORIGINS = {1: (301, 1207), 2: (1739, 85), 3: (911, 2011), 4: (2125, 1499)}     # (y0, x0) of faces 1..4 at every R: no multiple of 32
+# Inside the windows make_texture's +-1.5 white noise is divided by 64 and rides on +-1.5 noise of 8-texel cells, bilinearly
+# interpolated.  The float32 statement's address is off by about R 2^-23 texel (5e-4 at R = 7168), the same for all pairs of an
+# address at rest: `color` moves by that times the step between neighbouring texels, and the UV-chain moments (dL/dcol is a
+# difference of texels weighted with the other axis' fraction) by that times |second difference| / |first difference| of the cell,
+# which has no bound in white noise (measured: 1.2e-3 of sum|terms| at R = 7168 with white noise / 8, over the 1e-3 cap).
+BIG_CONTRAST = 1.0 / 64.0
+
+
+def big_window_block(g, size=BIG_WINDOW):
+    coarse = 1.5 * (2 * torch.rand(1, 3, size // 8 + 1, size // 8 + 1, generator=g, dtype=F64) - 1)
+    smooth = torch.nn.functional.interpolate(coarse, size=(size + 1, size + 1), mode="bilinear", align_corners=True)[0, :, :size, :size]
+    return (smooth.permute(1, 2, 0) + BIG_CONTRAST * 1.5 * (2 * torch.rand(size, size, 3, generator=g, dtype=F64) - 1)).to(F32)
+BIN_CHUNK = 32768                 # bins per trip of k_bin_offsets' loop (1024 threads x BO_MAX)
+
+
+def big_origins(R):
+    return [(0, 0)] + [BIG_ORIGINS[f] for f in (1, 2, 3, 4)] + [(R - BIG_WINDOW, R - BIG_WINDOW)]
+
+
+def build_uv_big(R):
+    """one tile, 96 entries, 16 per face, a 96x96-texel window per face of a texture of nominal resolution R (2368: the second trip
+    of k_bin_offsets' loop; 5462: the first allocation past 2^31 bytes; 7168: the limit of the ABI).  Face 0's window is the
+    top-left corner with footprints clamped at the left and top borders (one in the corner: texel 0), face 5's the bottom-right
+    corner with footprints clamped at the right and bottom borders (one in the corner: the last texel of the allocation) and
+    footprints in its last 8 rows and above them; the others lie inside their faces.  Nearly every address is at rest (a few 1e-3
+    texel per pixel, the fraction well inside its cell), four small fast splats per inner face sweep several cells: the cell bar
+    R 2^-20 texel is 6.8e-3 at R = 7168, and a large splat whose address sweeps many texels never settles."""
+    seed = 6000 + R
+    g = torch.Generator().manual_seed(seed)
+    u = lambda *s: torch.rand(*s, generator=g)
+    n = 96
+    r = _rec(n)
+    r[:, 0:2] = 16.0 * u(n, 2) - 0.5
+    s2 = (2.5 + 4.0 * u(n)) ** 2
+    r[:, 2], r[:, 4] = 1.0 / s2, 1.0 / (s2 * (0.6 + 0.8 * u(n)))
+    r[:, 3] = 0.5 * (2 * u(n) - 1) * torch.sqrt(r[:, 2] * r[:, 4])
+    r[:, 5] = 0.05 + 0.3 * u(n)
+    k = torch.arange(n)
+    face, j = k % 6, k // 6
+    fast = (face >= 1) & (face <= 4) & (j >= 12)          # sigma 0.5 px: a dozen pairs each, 0.3 texel per pixel
+    r[fast, 2] = r[fast, 4] = 4.0
+    r[fast, 3] = 0.0
+    r[fast, 5] = (0.3 + 0.4 * u(n))[fast]
+    r[fast, 0:2] = (2.0 + 12.0 * u(n, 2))[fast]
+    _fill_common(g, r, True, vd=0.3)
+    org = torch.tensor(big_origins(R), dtype=F64)
+    frac = lambda: 0.25 + 0.5 * u(n).to(F64)
+    lrow = torch.floor(12.0 + 72.0 * u(n)).to(F64) + frac()                      # inside the window, in texels from its origin
+    lcol = torch.floor(12.0 + 72.0 * u(n)).to(F64) + frac()
+    f5 = face == 5
+    lrow = torch.where(f5 & (j >= 12) & (j < 14), torch.floor(88.0 + 6.0 * u(n)).to(F64) + frac(), lrow)     # the last 8 rows, not clamped
+    lrow = torch.where(f5 & (j == 14), torch.floor(6.0 + 20.0 * u(n)).to(F64) + frac(), lrow)                # the window's first bin row
+    lrow = torch.where(f5 & (j == 15), torch.floor(40.0 + 20.0 * u(n)).to(F64) + frac(), lrow)
+    f0 = face == 0
+    lrow = torch.where(f0 & (j >= 12) & (j < 14), torch.floor(4.0 + 24.0 * u(n)).to(F64) + frac(), lrow)     # bin 0
+    lcol = torch.where(f0 & (j >= 12) & (j < 14), torch.floor(4.0 + 24.0 * u(n)).to(F64) + frac(), lcol)
+    row, col = org[face, 0] + lrow, org[face, 1] + lcol
+    # within half a texel of a border (both taps on one texel), yet GAP clear of the face edge: half a texel is 1.4e-4 of the major
+    # axis at R = 7168, so the address sits 0.41 .. 0.47 texel from the edge there (0.2 .. 0.47 at R = 2368), at rest
+    m_lo = max(0.2, 1.15 * GAP * 0.5 * R)
+    m = lambda: m_lo + (0.47 - m_lo) * u(n).to(F64)
+    lo, hi = -0.5 + m(), R - 0.5 - m()
+    col = torch.where((face == 0) & (j < 6), lo, torch.where(f5 & (j < 6), hi, col))
+    row = torch.where((face == 0) & ((j == 0) | ((j >= 6) & (j < 12))), lo, torch.where(f5 & ((j == 0) | ((j >= 6) & (j < 12))), hi, row))
+    speed = torch.where(fast, 0.3 * torch.ones(n), 0.001 + 0.002 * u(n))
+    speed = torch.where((f0 | f5) & (j < 12), 5e-5 + 5e-5 * u(n), speed)
+    r[:, 14:17] = direction(face, col, row, R).to(F32)
+    r[:, 8:14] = (torch.randn(n, 6, generator=g) * (speed * 2.0 / R)[:, None]).to(F32)
+    r[k % 4 == 1, 17:20] -= 0.6                         # negative viewdep: clamped channels
+    case = _single_tile(f"uv_big_R{R}", r, Windows(R, big_origins(R), [big_window_block(g) for _ in range(6)]), seed)
+    settle(case, seed, phi_nudge=0.02 * 2.0 / R)
+    cn = case.counters
+    with torch.no_grad():
+        t = _tile_forward(case, 0, case.rec.to(F64), case.texture.to(F64), F64)
+        c = t.contrib
+        on = lambda f, m: int((c & (t.face == f) & m).sum())
+        cn.update(clamp_left_face0=on(0, t.x0 < 0), clamp_top_face0=on(0, t.y0 < 0), clamp_right_face5=on(5, t.x0 >= R - 1),
+                  clamp_bottom_face5=on(5, t.y0 >= R - 1), first_texel=on(0, (t.x0 < 0) & (t.y0 < 0)),
+                  last_texel=on(5, (t.x0 >= R - 1) & (t.y0 >= R - 1)))
+        binned = c & (t.x0 >= 0) & (t.x0 < R - 1) & (t.y0 >= 0) & (t.y0 < R - 1)
+        nb = (R + 31) // 32
+        bins = ((t.face * nb + t.y0 // 32) * nb + t.x0 // 32)[binned]
+        byte = (((t.face * R + t.y0) * R + t.x0) * 12)[binned]
+        cn.update(bins=6 * nb * nb, pairs_binned=int(binned.sum()), pairs_bin0=int((bins == 0).sum()), pairs_below_chunk=int((bins < BIN_CHUNK).sum()),
+                  pairs_above_chunk=int((bins >= BIN_CHUNK).sum()), pairs_below_2_31=int((byte < 2 ** 31).sum()),
+                  pairs_above_2_31=int((byte >= 2 ** 31).sum()), pairs_face5_row_above_2_31=on(5, binned & (t.y0 * R * 12 + 5 * R * R * 12 >= 2 ** 31)),
+                  last_byte_offset=(6 * R * R - 1) * 12)
+    assert cn["faces"] == 6, cn
+    for b in ("clamp_left_face0", "clamp_top_face0", "clamp_right_face5", "clamp_bottom_face5"):
+        assert cn[b] >= 10, (b, cn)
+    assert cn["first_texel"] >= 1 and cn["last_texel"] >= 1, cn
+    assert cn["channel_clamped"] >= 20, cn
+    assert 6 * nb * nb > BIN_CHUNK and cn["pairs_bin0"] >= 10 and cn["pairs_below_chunk"] >= 100 and cn["pairs_above_chunk"] >= 100, cn
+    if 6 * R * R * 12 > 2 ** 31:
+        assert cn["pairs_below_2_31"] >= 100 and cn["pairs_above_2_31"] >= 100, cn
+    if R == 5462:                                       # byte 2^31 is texel (5, 5454, 2): footprints in the window's rows on both sides of it
+        assert cn["pairs_face5_row_above_2_31"] >= 10 and on(5, binned & (t.y0 < 5453)) >= 10, cn
+    return case
+
+
 COUNT_LENGTHS = [1023, 1024, 1100]
 
 
@@ -829,6 +1005,8 @@ for _W, _H in SIZES:
 for _R in RESOLUTIONS:
     CASES[f"uv_R{_R}"] = functools.partial(build_uv, _R)
 CASES["uv_R320"] = build_uv_320
+for _R in BIG_RESOLUTIONS:
+    CASES[f"uv_big_R{_R}"] = functools.partial(build_uv_big, _R)
 for _n in COUNT_LENGTHS:
     CASES[f"counts{_n}"] = functools.partial(build_counts, _n)
 for _n in (64, 65, 129):                                                      # case h: untextured
@@ -928,6 +1106,7 @@ def blend_f32(case):
         torch.use_deterministic_algorithms(was)
 
 
+@functools.lru_cache(maxsize=None)
 def statement_figures(name):
     """blend() in float32 against itself in float64: per image and per moment slot the worst error in units of the slot's
     sum|terms| -- the basis of the bars"""
@@ -951,7 +1130,28 @@ def statement_figures(name):
     return figs
 
 
-def base_bar(name, output):
+@functools.lru_cache(maxsize=None)
+def statement_figures_colour_only(name):
+    """statement_figures() of the colour-only pass (dL/ddepth, dL/dnorm, dL/dalpha absent): the moment slots and the texture
+    gradient.  There dL/dpower is made of colour terms alone, and a colour carries the float32 error of its tap address,
+    R 2^-23 texel times the step between texels: at R >= 5462 the M_P slots of that pass stand at 4e-5 .. 8e-5 of sum|terms| in the
+    float32 statement itself, 4 .. 8 x their figures in the full pass, where the depth / normal / alpha terms dilute them (with a
+    constant texture they are 4e-7 .. 8e-7 in both)."""
+    ref, f = prepared_colour_only(name), None
+    was = torch.are_deterministic_algorithms_enabled()
+    torch.use_deterministic_algorithms(True)
+    try:
+        f = blend(prepared(name).case, dtype=F32, colour_only=True)
+    finally:
+        torch.use_deterministic_algorithms(was)
+    figs = {"M_" + nm: unit_error(f.M[:, s], ref.M[:, s], ref.M_abs[:, s]) for s, nm in enumerate(MOMENT_NAMES)}
+    if ref.d_tex is not None:
+        figs["d_tex"], figs["d_tex_x"] = unit_error(f.d_tex, ref.d_tex, ref.d_tex_abs), unit_error(f.d_tex, ref.d_tex, ref.d_tex_x)
+    figs["n_contrib_equal"] = float(torch.equal(f.n_contrib, ref.n_contrib))
+    return figs
+
+
+def base_bar(name, output, section="f32_statement"):
     """max(4 x the f32 statement's figure of that case and output, 8 * 2^-24): the factor 4 is the margin preprocess_ref.hip_bar uses
     (device exp / reciprocal / fused multiply-adds differ from the host's by a few ulp through the same chain)"""
-    return max(4.0 * load_parity()["f32_statement"][name][output], FLOOR)
+    return max(4.0 * load_parity()[section][name][output], FLOOR)

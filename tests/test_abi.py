@@ -234,3 +234,32 @@ def test_uv_precision_is_checked_before_any_launch(lib_built):
         assert lib.texgs_uv_taylor_packed(C.byref(net), prec, b, None, 0, None, None, None) == 0, prec
         assert lib.texgs_uv_taylor_packed(C.byref(net), prec, b, None, -1, None, None, None) != 0, prec
         assert lib.texgs_uv_taylor_packed(C.byref(net), prec, b, None, 4, b, b, None) != 0 and b"NULL" in lib.texgs_last_error(), prec
+
+
+def test_texture_resolution_limit_is_checked_before_any_launch(lib_built):
+    """tex_res up to 7168 is accepted and 7169 refused by validate_frame, which runs before anything is launched (no GPU is needed to
+    see it): the blend kernels address texels with 32-bit BYTE offsets, and 6 * 7168^2 * 12 B = 3.7e9 is below 2^32.  The
+    texture-gradient bin count, which sizes tex_bin_count / tex_bin_cursor / tex_bin_base, is 301 056 there.  (The Python layer has
+    no check of its own: texgs.rasterizer takes R from the texture's shape and passes it on.)"""
+    import ctypes as C
+    from texgs import _lib
+    lib = _lib.load()
+    assert 2 ** 31 < 6 * 7168 ** 2 * 12 < 2 ** 32           # (7168 = 7 * 1024, a round number below sqrt(2^32 / 72) = 7723)
+    assert 6 * 7168 ** 2 * 12 - 12 == 3699376116
+    assert [int(lib.texgs_tex_bin_count(R)) for R in (1, 32, 33, 2336, 2368, 5462, 7168)] == [6, 6, 24, 31974, 32856, 175446, 301056]
+    buf = (C.c_float * 64)()              # stands in for every device pointer of the frame: a refused call reads none of them
+    b = C.addressof(buf)
+    frame = lambda R, N=0: _lib.Frame(16, 16, 1.0, 1.0, 1.0, 0, 0, R, N, 0, b, b, b, b)
+    inputs = _lib.Inputs(*([None] * 10))
+    geom = _lib.Geom(*([None] * 8), 0)
+    binning = _lib.Binning(0, None, None, None, None, None, None, 0)
+    image = _lib.Image(*([None] * 11))
+    assert lib.texgs_preprocess_forward(C.byref(frame(7168)), C.byref(inputs), C.byref(geom), None) == 0      # no Gaussians: valid, nothing to launch
+    for call in (lambda: lib.texgs_preprocess_forward(C.byref(frame(7169)), C.byref(inputs), C.byref(geom), None),
+                 lambda: lib.texgs_preprocess_forward(C.byref(frame(7169, 5)), C.byref(inputs), C.byref(geom), None),
+                 lambda: lib.texgs_render_forward(C.byref(frame(7169, 5)), C.byref(inputs), C.byref(geom), C.byref(binning), C.byref(image), None)):
+        assert lib.texgs_num_rendered_reduce(None, 4, None, None) != 0 and b"7168" not in lib.texgs_last_error()     # another message first
+        assert call() != 0
+        assert b"tex_res > 7168" in lib.texgs_last_error() and b"32-bit byte offsets" in lib.texgs_last_error()
+    with pytest.raises(RuntimeError, match=r"texgs_render_forward failed .*tex_res > 7168"):
+        _lib.call(lib.texgs_render_forward, C.byref(frame(7169, 5)), C.byref(inputs), C.byref(geom), C.byref(binning), C.byref(image), None)

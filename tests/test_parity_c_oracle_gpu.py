@@ -26,6 +26,7 @@ SIZES = {
     "small": (2000, 64, 200, 136, 0.02, 0),
     "c2": (100_000, 512, 800, 800, 0.006, 5),
     "c3": (300_000, 1024, 800, 800, 0.006, 0),
+    "bins32856": (2000, 2368, 64, 64, 0.02, 0),      # R = 2368: 6 * 74^2 = 32 856 texture-gradient bins, past one 32 768-bin trip of k_bin_offsets
 }
 _cache = {}
 
@@ -84,6 +85,40 @@ def test_backward_full_size_vs_c_oracle(lib_built, name):
                            tflag if name_ == "texture" else gflag)
     # the same gradients at PAIR level: every row checked, tolerance widened by what its own near-cell-edge pairs can contribute
     Hh.pair_level_gradient_check(f"hip_vs_c32/{name}/bwd_pair_level", ref, res, dout, scene.texture.shape[1], sens)
+
+
+def test_texture_of_more_than_32768_bins_vs_c_oracle(lib_built):
+    """One forward and backward through the rasterizer's host layer at R = 2368 (2 000 Gaussians, 64x64): 32 856 texture-gradient
+    bins, so tex_bin_count / tex_bin_cursor / tex_bin_base / the record lists are sized, zeroed and scanned past the 32 768 bins
+    that one trip of k_bin_offsets' loop handles, and the view's footprints fall into bins on both sides of that number.  Forward
+    and every gradient by attribution against the C oracle, as at the other sizes.  (The texture gradient is compared on the texels
+    either side touched -- 0.4 % of 33.6 M -- and is exactly 0 on both sides elsewhere.)"""
+    from texgs.rasterizer import backward_raw
+    from texgs import _lib
+    scene, cam, bg, ref, outs, s = _run("bins32856")
+    R, H, W = scene.texture.shape[1], cam.image_height, cam.image_width
+    nbins = int(_lib.load().texgs_tex_bin_count(R))
+    assert (R, nbins) == (2368, 32856) and s.tensors["tex_bin_count"].numel() == 2 * nbins
+    got = torch.cat([outs[0], outs[1], outs[2], outs[3]], 0)
+    Hh.forward_attributed("hip_vs_c32/bins32856/fwd", got, ref, ref.amb[0], n_contrib=s.tensors["n_contrib"].cpu().numpy().astype(np.uint32))
+    g = torch.Generator().manual_seed(77)
+    dout = torch.randn(8, H, W, generator=g) / (H * W)
+    dev = outs[0].device
+    res = backward_raw(s, dout[0:3].to(dev).contiguous(), dout[3:4].to(dev).contiguous(), dout[4:7].to(dev).contiguous(),
+                       dout[7:8].to(dev).contiguous())
+    gref = ref.backward(dout.numpy())
+    _, gflag, tflag = ref.amb
+    gflag = gflag | ref.accumulation_sensitive()
+    for name_, got_ in zip(["means3D", "means2D", "shs", "opacities", "scales", "rotations", "uvs"], res[:7]):
+        Hh.grad_attributed(f"hip_vs_c32/bins32856/bwd/{name_}", got_.cpu(), torch.tensor(gref[name_]), gflag)
+    exp_t = torch.as_tensor(gref["texture"]).reshape(-1, 3)
+    touched = ((res[7].reshape(-1, 3) != 0).any(1).cpu() | (exp_t != 0).any(1)).nonzero().reshape(-1)
+    nb = (R + 31) // 32
+    face, y, x = touched // (R * R), (touched // R) % R, touched % R
+    bins = (face * nb + y // 32) * nb + x // 32
+    assert int((bins < 32768).sum()) >= 100 and int((bins >= 32768).sum()) >= 100, (int((bins < 32768).sum()), int((bins >= 32768).sum()))
+    Hh.grad_attributed("hip_vs_c32/bins32856/bwd/texture", res[7].reshape(-1, 3)[touched.to(dev)].cpu(), exp_t[touched],
+                       torch.as_tensor(tflag).reshape(-1)[touched])
 
 
 def test_band_limited_texture_c3(lib_built):
