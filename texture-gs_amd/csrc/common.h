@@ -9,6 +9,7 @@
 #include "texgs_present.h"
 #include "texgs_ingest.h"
 #include "texgs_surface.h"
+#include "texgs_lpips.h"
 
 // ---- operator constants (restated in oracle/texgs_torch.py) ----
 #define TG_NEAR_Z        0.2f
@@ -150,3 +151,8 @@ hipError_t launch_rgba_composite(const uint8_t* rgba, uint8_t* out, int H, int W
 size_t surface_temp_bytes(int H, int W);             // the arguments of these are validated by the caller (abi.hip)
 hipError_t launch_surface_points(const TexGSSurfacePoints* p, void* temp, hipStream_t s);
 hipError_t launch_surface_compose(const TexGSSurfaceCompose* c, hipStream_t s);
+size_t conv3x3_packed_bytes(int Cin, int Cout);     // the arguments of these are validated by the caller (abi.hip)
+hipError_t launch_conv3x3_pack(const float* w, int Cin, int Cout, void* packed, hipStream_t s);
+hipError_t launch_conv3x3(const TexGSConv3x3* d, hipStream_t s);
+size_t lpips_head_temp_bytes(int P, int h, int w);
+hipError_t launch_lpips_head(const TexGSLpipsHead* d, hipStream_t s);

@@ -8,7 +8,9 @@ skimage.metrics.structural_similarity(channel_axis=0, data_range=1.0) -- uniform
 -- NOT the training loss of texgs.losses (11x11 Gaussian window, zero padding, population covariance).  Images are float32 [3,H,W]
 with H, W >= 7 (the window has to fit; skimage raises too), contiguous, on the GPU: there is no CPU fallback.
 
-Not here: LPIPS (its network weights are not part of this project).  The depth picture of train.py:22-37 is texgs.present.depth_colour;
+LPIPS-VGG is texgs.lpips (thirteen MFMA convolutions and a head in csrc/lpips.hip): `lpips(img1, img2, net)` below keeps the
+reference's signature, `Evaluator(capacity, lpips=net)` adds its column.  Its network weights are not part of this project: the
+user builds the net from the two published state dicts (texgs.lpips.LPIPSVGG).  The depth picture of train.py:22-37 is texgs.present.depth_colour;
 OpenCV's own JET table comes in through its `lut=` argument."""
 import numpy as np
 import torch
@@ -112,6 +114,30 @@ def mae(norm1, norm2, alpha=None):
     return (r[7] / r[8]).to(torch.float32)
 
 
+_default_lpips = None
+
+
+def set_lpips(net):
+    """Install the module default that `lpips(img1, img2)` uses: a texgs.lpips.LPIPSVGG, or None to remove it"""
+    global _default_lpips
+    _default_lpips = net
+
+
+def lpips(img1, img2, net=None):
+    """utils/metrics.py:49-58: LPIPS-VGG of ONE pair of [3,H,W] (or [1,3,H,W]) images in [0,1] (`normalize=True`), a Python float
+    from one readback.  `net`: a texgs.lpips.LPIPSVGG, else the default installed with `set_lpips`.  Several pairs have no single
+    float: they are refused by name (call the net itself for a [P,1,1,1] tensor)."""
+    net = _default_lpips if net is None else net
+    if net is None:
+        raise RuntimeError("no LPIPS network: build one with texgs.lpips.LPIPSVGG(vgg_state, lin_state) -- torchvision's VGG16 state "
+                           "dict and the lpips package's vgg.pth -- and pass it as net= or install it with texgs.metrics.set_lpips(net)")
+    for name, t in (("img1", img1), ("img2", img2)):
+        if torch.is_tensor(t) and t.dim() == 4 and t.shape[0] != 1:
+            raise ValueError(f"metrics.lpips returns one float for one pair; {name} holds {t.shape[0]} images: call net(img1, img2, "
+                             "normalize=True) for a [P,1,1,1] tensor")
+    return net(img1, img2, normalize=True).item()
+
+
 def avg_error(psnr, ssim, lpips):
     """The 'average' error used in the paper (utils/metrics.py:60-67), host arithmetic."""
     def psnr_to_mse(psnr):
@@ -150,15 +176,21 @@ class Evaluator:
             ev.add(image, gt_image, norm=norm, gt_norm=gt_normal, alpha=gt_alpha)     # enqueues; synchronises nothing
         res = ev.result()                                                             # one readback
 
-    `clamp=True` clamps image and gt_image to [0, 1] in the kernel (train.py:52,58); normals and alpha are never clamped."""
+    `clamp=True` clamps image and gt_image to [0, 1] in the kernel (train.py:52,58); normals and alpha are never clamped.
 
-    def __init__(self, capacity):
+    `Evaluator(capacity, lpips=net)` with a texgs.lpips.LPIPSVGG: `add` also enqueues the LPIPS (`normalize=True`) of the pair --
+    clamped when `clamp` -- into a second device table, still without synchronising anything; `result` reads that table in the same
+    call and adds "lpips" (the mean over views) and "avg_error" (of the three means).  Without it nothing changes."""
+
+    def __init__(self, capacity, lpips=None):
         capacity = int(capacity)
         if capacity < 1:
             raise ValueError("capacity must be at least 1")
         self.capacity = capacity
         self._table = None          # f64 [capacity, 16] on the device of the first view
         self._has_norm = []
+        self._lpips = lpips
+        self._lpips_table = None    # f64 [capacity, 8] (texgs.lpips.ROW) next to it
 
     def __len__(self):
         return len(self._has_norm)
@@ -174,6 +206,12 @@ class Evaluator:
         elif self._table.device != image.device:
             raise ValueError(f"image is on {image.device}, the earlier views were on {self._table.device}")
         _launch(image, gt_image, norm, gt_norm, alpha, H, W, clamp, self._table, v)
+        if self._lpips is not None:
+            if self._lpips_table is None:
+                from .lpips import ROW as LPIPS_ROW
+                self._lpips_table = torch.zeros(self.capacity, LPIPS_ROW, dtype=torch.float64, device=image.device)
+            a, b = (image.clamp(0.0, 1.0), gt_image.clamp(0.0, 1.0)) if clamp else (image, gt_image)
+            self._lpips.table(a, b, normalize=True, out=self._lpips_table[v:v + 1])
         self._has_norm.append(norm is not None)
 
     def rows(self):
@@ -185,4 +223,14 @@ class Evaluator:
 
     def result(self):
         rows = self.rows()
-        return finish_rows(rows.cpu().numpy(), self._has_norm)
+        if self._lpips is None:
+            return finish_rows(rows.cpu().numpy(), self._has_norm)
+        v = len(self._has_norm)
+        if v == 0:
+            return dict(finish_rows(rows.cpu().numpy(), self._has_norm), lpips=None, avg_error=None)
+        from .lpips import LAYERS
+        both = torch.cat([rows, self._lpips_table[:v]], dim=1).cpu().numpy()          # one readback
+        res = finish_rows(both[:, :ROW], self._has_norm)
+        res["lpips"] = float(both[:, ROW + LAYERS].mean())
+        res["avg_error"] = avg_error(res["psnr"], res["ssim"], res["lpips"])
+        return res
