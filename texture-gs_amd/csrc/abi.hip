@@ -897,6 +897,33 @@ int texgs_lpips_head(const TexGSLpipsHead* d, void* stream) {
     return launched("lpips_head", launch_lpips_head(d, s), s, false);
 }
 
+// include/texgs_lpips_grad.h
+int texgs_lpips_head_backward(const TexGSLpipsHeadBackward* d, void* stream) {
+    if (!d) return fail_msg("head backward descriptor is NULL");
+    if (int r = check_lpips_head_size(d->P, d->h, d->w)) return r;
+    if (d->C < 1 || d->C > TEXGS_CONV_MAX_CHANNELS) { snprintf(g_err, sizeof(g_err), "C must be in [1,512], got %d", (int)d->C); return -1; }
+    if (d->wrt < 1 || d->wrt > (TEXGS_LPIPS_WRT_FIRST | TEXGS_LPIPS_WRT_PARTNER)) {
+        snprintf(g_err, sizeof(g_err), "wrt must be 1 (first images), 2 (partners) or 3 (both), got %d", (int)d->wrt);
+        return -1;
+    }
+    if (d->g_next && (d->h < 2 || d->w < 2)) return fail_msg("g_next needs h and w of at least 2: the pooled map would be empty");
+    const int64_t Bg = d->wrt == 3 ? 2 * (int64_t)d->P : d->P;
+    if (int r = check_conv_strides("g", d->g_row, d->g_chan, d->g_img, Bg, d->C, d->h, d->w)) return r;
+    if (!d->f || !d->lin || !d->gbar || !d->G) return fail_msg("NULL argument (f, lin, gbar or G)");
+    if (((uintptr_t)d->f | (uintptr_t)d->lin | (uintptr_t)d->gbar | (uintptr_t)d->g_next | (uintptr_t)d->G) & 3)
+        return fail_msg("f, lin, gbar, g_next and G must be 4-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    return launched("lpips_head_backward", launch_lpips_head_backward(d, s), s, false);
+}
+
+int texgs_lpips_gate(float* G, const float* y, int64_t n, void* stream) {
+    if (n < 1 || n >= (1ll << 40)) { snprintf(g_err, sizeof(g_err), "n must be in [1,2^40), got %lld", (long long)n); return -1; }
+    if (!G || !y) return fail_msg("NULL argument (G or y)");
+    if (((uintptr_t)G | (uintptr_t)y) & 15) return fail_msg("G and y must be 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    return launched("lpips_gate", launch_lpips_gate(G, y, n, s), s, false);
+}
+
 int texgs_selftest_waveops(const float* seed128, float* out576, void* stream) {
     if (!seed128 || !out576) return fail_msg("NULL argument");
     return launched("selftest_waveops", launch_selftest_waveops(seed128, out576, (hipStream_t)stream), (hipStream_t)stream, false);

@@ -10,6 +10,7 @@
 #include "texgs_ingest.h"
 #include "texgs_surface.h"
 #include "texgs_lpips.h"
+#include "texgs_lpips_grad.h"
 
 // ---- operator constants (restated in oracle/texgs_torch.py) ----
 #define TG_NEAR_Z        0.2f
@@ -156,3 +157,5 @@ hipError_t launch_conv3x3_pack(const float* w, int Cin, int Cout, void* packed, 
 hipError_t launch_conv3x3(const TexGSConv3x3* d, hipStream_t s);
 size_t lpips_head_temp_bytes(int P, int h, int w);
 hipError_t launch_lpips_head(const TexGSLpipsHead* d, hipStream_t s);
+hipError_t launch_lpips_head_backward(const TexGSLpipsHeadBackward* d, hipStream_t s);      // lpips_grad.hip, validated by abi.hip
+hipError_t launch_lpips_gate(float* G, const float* y, long long n, hipStream_t s);

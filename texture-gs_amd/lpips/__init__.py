@@ -14,7 +14,9 @@ and a FileNotFoundError names both files and both variables when one is missing.
 
 Only `net="vgg"`, version 0.1, the scalar metric: `net="alex"` / `"squeeze"`, `spatial=True`, `lpips=False`, `pretrained=False`
 and `retPerLayer=True` raise NotImplementedError by name.  The architecture is restated from the package's published source and is
-UNPINNED (texgs.lpips says so in a RuntimeWarning).  There is no backward and no CPU fallback."""
+UNPINNED (texgs.lpips says so in a RuntimeWarning).  As in the package, the value is differentiable in the two images -- with grad
+mode on and an input that requires grad, `backward()` fills its `.grad` (texgs/lpips_grad.py; once per forward, no double backward,
+the weights are constants).  There is no CPU fallback."""
 import os
 
 import torch

@@ -25,8 +25,13 @@ ping-pong activation buffers, each as large as the largest map (`activation_floa
 Precision: "fp32" -- f32-input MFMA, exact f32 products in a k-ordered f32 chain.  "bf16x3" (TEXGS_LPIPS_BF16X3) is reserved and
 refused by name: it is not built.
 
-Inputs are detached and there is NO backward: LPIPS is an evaluation metric in the reference, not a loss.  No CPU fallback: CPU
-tensors raise.  Every argument is checked here, before any library call (tests/lpips_ref.py holds the float64 statement)."""
+Backward: calling the net with grad mode on and an image that requires grad returns a value that is differentiable in the images
+(texgs/lpips_grad.py, csrc/lpips_grad.hip): the same launches and the same bits as the no-grad call, but the thirteen post-ReLU maps
+are kept for the backward (`grad_activation_floats`: 345.6 M floats, 1.38 GB, for one 800x800 pair) instead of two ping-pong buffers.
+The backward runs the thirteen data gradients through the same convolution kernel over transposed weights and returns f32 gradients
+of img0 and img1 (None for one that does not require grad; with one of them the convolutions run over P images, not 2P).  It runs
+once per forward, a double backward raises, and the weights are constants.  `table`, `layers`, `features`, texgs.metrics.lpips and
+Evaluator never take this path: they detach.  No CPU fallback: CPU tensors raise.  Every argument is checked here, before any library call (tests/lpips_ref.py holds the float64 statement)."""
 import ctypes as C
 import math
 import warnings
@@ -296,6 +301,17 @@ def activation_floats(B, H, W, widths=WIDTHS):
     return need
 
 
+def grad_activation_floats(P, H, W, widths=WIDTHS):
+    """Floats of the thirteen post-ReLU maps that a differentiable call keeps until its backward, for P pairs of H x W: every
+    convolution of slice s writes 2P x widths[s] x (H >> s) x (W >> s).  345.6 M floats (1.38 GB) for one 800x800 pair."""
+    need, h, w = 0, int(H), int(W)
+    for s, (c, n) in enumerate(zip(widths, SLICES)):
+        if s > 0:
+            h, w = out_size(h, w, True)
+        need += n * 2 * int(P) * int(c) * h * w
+    return need
+
+
 def _check_images(img0, img1):
     """Everything a launch relies on, before any library call -> (img0, img1 as [P,3,H,W], unbatched)"""
     for name, t in (("img0", img0), ("img1", img1)):
@@ -324,7 +340,8 @@ def _check_images(img0, img1):
 
 
 class LPIPSVGG:
-    """The metric as an object (module docstring).  Not an nn.Module: it has no parameters to train and no backward."""
+    """The metric as an object (module docstring).  Not an nn.Module: it has no parameters to train; it is differentiable in the
+    images only."""
 
     def __init__(self, vgg_state, lin_state, precision="fp32", widths=WIDTHS, _warn=True):
         _precision(precision)
@@ -337,6 +354,7 @@ class LPIPSVGG:
         self.convs = vgg_tensors(_load_state(vgg_state, "vgg_state"), self.widths)      # host copies: [(w, b)] x 13
         self.lins = lin_tensors(_load_state(lin_state, "lin_state"), self.widths)       # [lin] x 5
         self._device = {}                                                               # (device, precision) -> packed weights
+        self._device_grad = {}                                                          # likewise, the data gradients' (transposed)
         if _warn:
             warnings.warn("LPIPSVGG restates the architecture of lpips 0.1 (scaling layer, taps, pools, head) from its published "
                           "source; it is UNPINNED against the real package, which cannot be imported here", RuntimeWarning, stacklevel=2)
@@ -379,9 +397,11 @@ class LPIPSVGG:
             self._device[key] = w
         return w
 
-    def _run(self, x, normalize, table=None, keep=False):
+    def _run(self, x, normalize, table=None, keep=False, keep_all=False):
         """x f32 [B,3,H,W] through the thirteen convolutions on the current stream.  With `table` (f64 [B/2, 8]) the head of a slice
-        runs as soon as the slice is done; with `keep` the five tapped maps are cloned and returned."""
+        runs as soon as the slice is done; with `keep` the five tapped maps are cloned and returned.  With `keep_all` every
+        convolution writes a buffer of its own instead of the two ping-pong ones and the thirteen maps are returned: the same
+        launches, so the same bits."""
         lib = entry()
         dev = x.device
         wts = self._weights(dev)
@@ -390,15 +410,20 @@ class LPIPSVGG:
         if B * H * W >= 2 ** 31:
             raise ValueError(f"{B} images of {H}x{W} hold 2^31 pixels or more")
         scale, shift = wts["affine"][bool(normalize)]
-        bufs = [torch.empty(activation_floats(B, H, W, self.widths), dtype=torch.float32, device=dev) for _ in range(2)]
-        taps = []
+        bufs = [] if keep_all else [torch.empty(activation_floats(B, H, W, self.widths), dtype=torch.float32, device=dev) for _ in range(2)]
+        taps, maps = [], []
         with _lib.on(dev) as stream:
             src_ptr, cur, h, w, k = x.data_ptr(), 0, H, W, 0
             for s, n in enumerate(SLICES):
                 for j in range(n):
                     packed, bias, cin, cout = wts["convs"][k]
                     pool = s > 0 and j == 0
-                    dst = bufs[cur]
+                    if keep_all:
+                        ho, wo = out_size(h, w, pool)
+                        dst = torch.empty(B, cout, ho, wo, dtype=torch.float32, device=dev)
+                        maps.append(dst)
+                    else:
+                        dst = bufs[cur]
                     _conv(lib, stream, src_ptr, packed, bias, scale if k == 0 else None, shift if k == 0 else None, dst.data_ptr(),
                           B, cin, cout, h, w, True, pool, prec)
                     h, w = out_size(h, w, pool)
@@ -406,8 +431,8 @@ class LPIPSVGG:
                 if table is not None:
                     _head(lib, stream, src_ptr, wts["lins"][s], table, B // 2, self.widths[s], h, w, s)
                 if keep:
-                    taps.append(bufs[1 - cur][:B * self.widths[s] * h * w].view(B, self.widths[s], h, w).clone())
-        return taps
+                    taps.append(dst.view(-1)[:B * self.widths[s] * h * w].view(B, self.widths[s], h, w).clone())
+        return maps if keep_all else taps
 
     def table(self, img0, img1, normalize=False, out=None):
         """The raw rows f64 [P, 8] on the device (columns 0-4 the layers' terms, 5 their sum); `out`: a caller-owned [P, 8] slice"""
@@ -432,8 +457,85 @@ class LPIPSVGG:
         x, _, _ = _check_images(x, x)
         return self._run(x, normalize, keep=True)
 
+    # ---- the differentiable path (texgs/lpips_grad.py) ----
+    def _grad_weights(self, device):
+        """The data gradients' weights on `device`: per convolution (packed transposed weights, a zero bias, channels in, channels
+        out), packed once per (device, precision)"""
+        from . import lpips_grad as G
+        key = (device, self.precision)
+        w = self._device_grad.get(key)
+        if w is None:
+            w = []
+            for wt, _ in self.convs:
+                t = G.transposed_weight(wt).to(device)
+                w.append((pack_conv3x3(t, self.precision), torch.zeros(t.shape[0], dtype=torch.float32, device=device), int(t.shape[1]),
+                          int(t.shape[0])))
+            self._device_grad[key] = w
+        return w
+
+    def _forward_grad(self, img0, img1, normalize):
+        """The value as __call__ returns it, by the same launches, and what the backward needs: the thirteen post-ReLU maps"""
+        img0, img1, unbatched = _check_images(img0, img1)
+        P, _, H, W = (int(v) for v in img0.shape)
+        table = torch.zeros(P, ROW, dtype=torch.float64, device=img0.device)
+        maps = self._run(torch.cat([img0, img1]), normalize, table=table, keep_all=True)
+        state = dict(maps=maps, P=P, H=H, W=W, normalize=bool(normalize), unbatched=unbatched, device=img0.device)
+        return table[:, LAYERS].to(torch.float32).view(-1, 1, 1, 1), state
+
+    def _backward_grad(self, state, gbar, wrt):
+        """(d img0, d img1) f32 from `state` (of _forward_grad), gbar f32 [P] and wrt (1: img0, 2: img1, 3: both); None for an image
+        that `wrt` leaves out.  Per slice, last first: the head's backward writes the gradient at the tapped convolution's
+        output; then, per convolution, its data gradient (conv3x3 over the transposed weights) and the gate of the convolution in
+        front -- or, at the head of a slice, the hand-over to the next head's backward, which routes it through the pool."""
+        from . import lpips_grad as G
+        wrt = G.check_wrt(wrt)
+        lib, glib = entry(), G.entry()
+        dev, P, H, W, maps = state["device"], state["P"], state["H"], state["W"], state["maps"]
+        if maps is None:
+            raise RuntimeError("LPIPSVGG: this forward's activations were consumed by an earlier backward")
+        if not torch.is_tensor(gbar) or tuple(gbar.shape) != (P,) or gbar.dtype != torch.float32 or not gbar.is_contiguous() \
+                or gbar.device != dev:
+            raise ValueError(f"gbar must be a contiguous float32 [{P}] on {dev}")
+        state["maps"] = None
+        wts, gw = self._weights(dev), self._grad_weights(dev)
+        prec = PRECISION[self.precision]
+        Bg = G.selected(P, wrt)
+        sizes = [(H, W)]
+        for _ in range(1, LAYERS):
+            sizes.append(out_size(*sizes[-1], True))
+        new = lambda c, h, w: torch.empty(Bg * c * h * w, dtype=torch.float32, device=dev)
+        with _lib.on(dev) as stream:
+            k, g_next = len(maps) - 1, None
+            for s in reversed(range(LAYERS)):
+                (h, w), Cn = sizes[s], self.widths[s]
+                grad = new(Cn, h, w)
+                G._head_backward(glib, stream, maps[k].data_ptr(), wts["lins"][s], gbar, _lib.ptr(g_next), grad.data_ptr(), P, Cn, h, w, wrt)
+                for j in reversed(range(SLICES[s])):
+                    packed, zero, cin, cout = gw[k]
+                    gin = new(cout, h, w)
+                    _conv(lib, stream, grad.data_ptr(), packed, zero, None, None, gin.data_ptr(), Bg, cin, cout, h, w, False, False, prec)
+                    if j > 0:                   # the partners' half of a kept map starts P images in
+                        y_ptr = maps[k - 1].data_ptr() + (4 * P * cout * h * w if wrt == G.WRT_PARTNER else 0)
+                        G._gate(glib, stream, gin.data_ptr(), y_ptr, Bg * cout * h * w)
+                        grad = gin
+                    else:
+                        g_next = gin
+                    maps[k] = None
+                    k -= 1
+            scale = wts["affine"][state["normalize"]][0]
+            d = g_next.view(Bg, -1, H, W)[:, :3] * scale.view(1, 3, 1, 1)
+        d0 = d[:P] if wrt & G.WRT_FIRST else None
+        d1 = (d[P:] if wrt == 3 else d) if wrt & G.WRT_PARTNER else None
+        if state["unbatched"]:
+            d0, d1 = (None if t is None else t[0] for t in (d0, d1))
+        return d0, d1
+
     def __call__(self, img0, img1, normalize=False):
-        """f32 [P,1,1,1] ([1,1,1,1] for unbatched input: the package's shape), on the device; nothing is read back"""
+        """f32 [P,1,1,1] ([1,1,1,1] for unbatched input: the package's shape), on the device; nothing is read back.  With grad mode
+        on and an image that requires grad the value is differentiable in the images (module docstring)."""
+        if torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in (img0, img1)):
+            from . import lpips_grad as G
+            return G.LpipsFunction.apply(img0, img1, self, bool(normalize))
         return self.table(img0, img1, normalize)[:, LAYERS].to(torch.float32).view(-1, 1, 1, 1)
 
     forward = __call__

@@ -135,7 +135,8 @@ def lpips(img1, img2, net=None):
         if torch.is_tensor(t) and t.dim() == 4 and t.shape[0] != 1:
             raise ValueError(f"metrics.lpips returns one float for one pair; {name} holds {t.shape[0]} images: call net(img1, img2, "
                              "normalize=True) for a [P,1,1,1] tensor")
-    return net(img1, img2, normalize=True).item()
+    with torch.no_grad():               # a metric: never the differentiable path, whatever the images require
+        return net(img1, img2, normalize=True).item()
 
 
 def avg_error(psnr, ssim, lpips):
