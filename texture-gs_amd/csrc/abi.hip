@@ -586,6 +586,88 @@ int texgs_sh_flush(int32_t N, int32_t K, const float* means3D, const float* shs,
     return launched("sh_flush", launch_sh_flush(N, K, means3D, shs, dL_dshs, dL_dmeans3D, views, count, s), s, false);
 }
 
+// include/texgs_multiview.h, the batched front end: what the views of one batch must share, by name; nothing is launched on a refusal
+static int check_views(const TexGSFrame* frames, int32_t count) {
+    if (!frames) return fail_msg("frames is NULL");
+    if (count < 1) return fail_msg("count < 1");
+    if (count > TEXGS_BATCH_MAX_VIEWS) return fail_msg("count exceeds TEXGS_BATCH_MAX_VIEWS: batch in several calls or take the per-view path");
+    for (int32_t v = 0; v < count; ++v) {
+        if (int r = validate_frame(&frames[v])) return r;
+        const TexGSFrame &a = frames[0], &b = frames[v];
+        if (a.image_height != b.image_height || a.image_width != b.image_width) return fail_msg("the views of a batch must have one image size");
+        if (a.num_gaussians != b.num_gaussians) return fail_msg("the views of a batch must have one num_gaussians");
+        if (a.sh_degree != b.sh_degree || a.sh_coeffs != b.sh_coeffs) return fail_msg("the views of a batch must have one sh_degree and one sh_coeffs");
+        if ((a.debug != 0) != (b.debug != 0)) return fail_msg("the views of a batch must have one debug flag");
+    }
+    if (frames[0].num_gaussians == 0) return fail_msg("num_gaussians == 0: nothing to batch, take the per-view path");
+    return 0;
+}
+
+int texgs_preprocess_forward_views(const TexGSFrame* frames, const TexGSInputs* in, TexGSGeom* geoms, int32_t count, uint32_t* sums,
+                                   void* stream) {
+    if (int r = check_views(frames, count)) return r;
+    if (!in || !geoms || !sums) return fail_msg("NULL argument");
+    if (!in->means3D || !in->opacities) return fail_msg("per-Gaussian input pointer is NULL");
+    if (in->texture && (!in->uvs || !in->gradient_uvs)) return fail_msg("uvs / gradient_uvs are required with a texture");
+    if (in->cov3D_precomp && in->texture) return fail_msg("cov3D_precomp is an input of the untextured surface only (texture must be NULL)");
+    if (!in->cov3D_precomp && (!in->scales || !in->rotations)) return fail_msg("scales and rotations (or cov3D_precomp) are required");
+    for (int32_t v = 0; v < count; ++v) {
+        const TexGSGeom& g = geoms[v];
+        if (!g.rec_test || !g.rec_shade || !g.depth || !g.radii || !g.rect || !g.tiles_touched || !g.scan_temp) return fail_msg("NULL buffer in a view's TexGSGeom");
+        if (g.scan_temp_bytes < scan_temp_bytes(frames[0].num_gaussians)) return fail_msg("scan_temp too small");
+    }
+    hipStream_t s = (hipStream_t)stream;
+    hipError_t st;
+    { ProfScope p(TEXGS_K_PREPROCESS_FWD, s); st = launch_preprocess_fwd_views(frames, in, geoms, count, sums, s); }
+    return launched("preprocess_fwd (views)", st, s, frames[0].debug);
+}
+
+int texgs_depth_sort_scan_views(const TexGSGeom* geoms, int32_t num_gaussians, int32_t count, void* stream) {
+    if (!geoms) return fail_msg("NULL argument");
+    if (count < 1 || count > TEXGS_BATCH_MAX_VIEWS) return fail_msg("count must be in [1, TEXGS_BATCH_MAX_VIEWS]");
+    if (num_gaussians <= 0) return fail_msg("num_gaussians must be positive");
+    for (int32_t v = 0; v < count; ++v) {
+        if (!geoms[v].depth || !geoms[v].tiles_touched || !geoms[v].scan_temp) return fail_msg("NULL buffer in a view's TexGSGeom");
+        if (geoms[v].scan_temp_bytes < scan_temp_bytes(num_gaussians)) return fail_msg("scan_temp too small");
+    }
+    hipStream_t s = (hipStream_t)stream;
+    hipError_t st;
+    { ProfScope p(TEXGS_K_SCAN, s); st = launch_depth_sort_scan_views(geoms, num_gaussians, count, s); }
+    return launched("depth sort / scan (views)", st, s, false);
+}
+
+int texgs_bin_sort_views(const TexGSFrame* frames, const TexGSGeom* geoms, TexGSBinning* bins, const TexGSImage* imgs, int32_t count,
+                         void* stream) {
+    if (int r = check_views(frames, count)) return r;
+    if (!geoms || !bins || !imgs) return fail_msg("NULL argument");
+    const CamConst c = make_cam(&frames[0]);
+    const uint32_t T = (uint32_t)(c.tiles_x * c.tiles_y);
+    for (int32_t v = 0; v < count; ++v) {
+        const TexGSBinning& b = bins[v];
+        if (!geoms[v].offsets || !geoms[v].rect || !geoms[v].tiles_touched || !geoms[v].scan_temp) return fail_msg("NULL buffer in a view's TexGSGeom");
+        if (!b.ranges || !b.tile_order) return fail_msg("NULL ranges / tile_order in a view's TexGSBinning");
+        if (b.num_rendered > 0) {
+            if (!b.keys_unsorted || !b.keys_sorted || !b.point_list || !b.sort_temp) return fail_msg("NULL buffer in a view's TexGSBinning");
+            if (b.sort_temp_bytes < sort_temp_bytes(b.num_rendered, T)) return fail_msg("sort_temp too small");
+        }
+        if ((imgs[v].tex_bin_count != nullptr) && frames[v].tex_res != frames[0].tex_res) return fail_msg("the views of a batch must have one tex_res");
+    }
+    hipStream_t s = (hipStream_t)stream;
+    hipError_t st;
+    const int nzw = 2 * (int)tex_bin_count(c.R);
+    { ProfScope p(TEXGS_K_DUPLICATE, s); st = launch_bin_views(TEXGS_K_DUPLICATE, c, geoms, bins, imgs, count, nzw, s); }
+    if (int r = launched("duplicate_with_keys (views)", st, s, frames[0].debug)) return r;
+    { ProfScope p(TEXGS_K_SORT, s); st = launch_bin_views(TEXGS_K_SORT, c, geoms, bins, imgs, count, nzw, s); }
+    if (int r = launched("tile sort (views)", st, s, frames[0].debug)) return r;
+    { ProfScope p(TEXGS_K_RANGES, s); st = launch_bin_views(TEXGS_K_RANGES, c, geoms, bins, imgs, count, nzw, s); }
+    return launched("tile_ranges (views)", st, s, frames[0].debug);
+}
+
+int texgs_render_forward_binned(const TexGSFrame* frame, const TexGSInputs* in, const TexGSGeom* geom, const TexGSBinning* bin,
+                                TexGSImage* img, void* stream) {
+    return render_forward_impl(frame, in, geom, bin, img, stream, true);
+}
+
 // include/texgs_mlp.h: the shape, by name
 static int check_mlp(const TexGSMlp* m) {
     if (!m) return fail_msg("mlp is NULL");

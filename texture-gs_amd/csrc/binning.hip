@@ -44,12 +44,13 @@ __device__ __forceinline__ void block_range(uint32_t n, uint32_t per, uint32_t& 
     hi = min(n, lo + per);
 }
 
+// The kernels of this file are written as `*_body` device functions with two __global__ entries each: the single-view kernel (the
+// body on its arguments) and a `*_views` one for the batched front end (texgs_multiview.h), which takes the view as blockIdx.y, picks
+// that view's pointers and counts out of a by-value table and runs the same body -- so a view's results are the single-view
+// kernel's, bit for bit.  The bodies only use blockIdx.x / gridDim.x.
 template <typename KEY>
-__global__ void __launch_bounds__(RS_THREADS)
-k_radix_count(const KEY* __restrict__ keys, const uint32_t* __restrict__ n_ptr, uint32_t n_max, uint32_t per, int shift,
-              uint32_t mask, RadixTables t) {
+__device__ __forceinline__ void radix_count_body(const KEY* __restrict__ keys, uint32_t n, uint32_t per, int shift, uint32_t mask, RadixTables t) {
     __shared__ uint32_t s_hist[256];
-    const uint32_t n = n_ptr ? min(*n_ptr, n_max) : n_max;
     uint32_t lo, hi;
     block_range(n, per, lo, hi);
     s_hist[threadIdx.x] = 0u;
@@ -69,18 +70,24 @@ k_radix_count(const KEY* __restrict__ keys, const uint32_t* __restrict__ n_ptr, 
     if (c != 0u) atomicAdd(&t.gtable[(blockIdx.x / RS_GROUP) * 256 + threadIdx.x], c);
 }
 
+template <typename KEY>
+__global__ void __launch_bounds__(RS_THREADS)
+k_radix_count(const KEY* __restrict__ keys, const uint32_t* __restrict__ n_ptr, uint32_t n_max, uint32_t per, int shift,
+              uint32_t mask, RadixTables t) {
+    radix_count_body<KEY>(keys, n_ptr ? min(*n_ptr, n_max) : n_max, per, shift, mask, t);
+}
+
 // MODE 0: pairs (u32 key, u32 val) -> pairs; val_in == nullptr means val = element index (first depth pass)
 // MODE 1: u64 elements -> u64 elements
 // MODE 2: u64 elements (tile << 32 | rank) -> keys_sorted = (tile << 32) | depth_rank[rank], point_list = id_rank[rank]
+// nblocks: the blocks of the pass (the count table's rows in use)
 template <typename KEY, int MODE>
-__global__ void __launch_bounds__(RS_THREADS)
-k_radix_scatter(const KEY* __restrict__ keys_in, const uint32_t* __restrict__ vals_in, KEY* __restrict__ keys_out,
-                uint32_t* __restrict__ vals_out, const uint32_t* __restrict__ n_ptr, uint32_t n_max, uint32_t per, int shift,
+__device__ __forceinline__ void radix_scatter_body(const KEY* __restrict__ keys_in, const uint32_t* __restrict__ vals_in, KEY* __restrict__ keys_out,
+                uint32_t* __restrict__ vals_out, uint32_t n, uint32_t nblocks, uint32_t per, int shift,
                 uint32_t mask, int bits, RadixTables t, const uint32_t* __restrict__ depth_rank,
                 const uint32_t* __restrict__ id_rank) {
     __shared__ uint32_t s_wcnt[4][256];          // per-wave digit counts, then running output cursors
     __shared__ uint32_t s_scan[256];
-    const uint32_t n = n_ptr ? min(*n_ptr, n_max) : n_max;
     uint32_t lo, hi;
     block_range(n, per, lo, hi);
     if (lo >= hi) return;
@@ -110,7 +117,7 @@ k_radix_scatter(const KEY* __restrict__ keys_in, const uint32_t* __restrict__ va
         // Every group row is read: the rows before this block's group count towards `before`, all of them towards the digit total.
         static_assert(RS_MAX_BLOCKS / RS_GROUP <= RS_GROUP, "one loop covers the group rows and the rows inside a group");
         const int g = blockIdx.x / RS_GROUP, inb = (int)blockIdx.x - g * RS_GROUP;
-        const int ngroups = ((int)gridDim.x + RS_GROUP - 1) / RS_GROUP;
+        const int ngroups = ((int)nblocks + RS_GROUP - 1) / RS_GROUP;
         uint32_t part[2 * RS_GROUP];
 #pragma unroll
         for (int k = 0; k < RS_GROUP; ++k) {
@@ -198,6 +205,16 @@ k_radix_scatter(const KEY* __restrict__ keys_in, const uint32_t* __restrict__ va
     }
 }
 
+template <typename KEY, int MODE>
+__global__ void __launch_bounds__(RS_THREADS)
+k_radix_scatter(const KEY* __restrict__ keys_in, const uint32_t* __restrict__ vals_in, KEY* __restrict__ keys_out,
+                uint32_t* __restrict__ vals_out, const uint32_t* __restrict__ n_ptr, uint32_t n_max, uint32_t per, int shift,
+                uint32_t mask, int bits, RadixTables t, const uint32_t* __restrict__ depth_rank,
+                const uint32_t* __restrict__ id_rank) {
+    radix_scatter_body<KEY, MODE>(keys_in, vals_in, keys_out, vals_out, n_ptr ? min(*n_ptr, n_max) : n_max, gridDim.x, per, shift, mask,
+                                  bits, t, depth_rank, id_rank);
+}
+
 // ---- K2, round 4: depth sort of the N Gaussians + exclusive scan of tiles_touched in rank order in THREE launches -------------
 // (round 3: four stable 8-bit radix passes = 8 launches, + 2 for the scan; every launch is one or two dependent round trips over
 // 2.4 MB on a chip it cannot fill: 64 us at C3, 46 us at C2.)  Now:
@@ -267,8 +284,7 @@ __device__ __forceinline__ uint32_t depth_bin(uint32_t key, uint32_t lo, uint32_
 }
 __device__ __forceinline__ uint32_t depth_bin(uint32_t key, const DepthRange& r) { return depth_bin(key, r.lo, r.scale, r.nb); }
 
-__global__ void __launch_bounds__(DS_THREADS)
-k_depth_count(const uint32_t* __restrict__ keys, int N, const uint32_t* __restrict__ block_D, int nblk, int lb, uint32_t* __restrict__ btot) {
+__device__ __forceinline__ void depth_count_body(const uint32_t* __restrict__ keys, int N, const uint32_t* __restrict__ block_D, int nblk, int lb, uint32_t* __restrict__ btot) {
     __shared__ uint32_t s_hist[DS_NB_MAX + 1];
     __shared__ uint32_t s_red[8];
     const int tid = threadIdx.x;
@@ -288,7 +304,11 @@ k_depth_count(const uint32_t* __restrict__ keys, int N, const uint32_t* __restri
 }
 
 __global__ void __launch_bounds__(DS_THREADS)
-k_depth_scatter(const uint32_t* __restrict__ keys, int N, const uint32_t* __restrict__ block_D, int nblk, int lb,
+k_depth_count(const uint32_t* __restrict__ keys, int N, const uint32_t* __restrict__ block_D, int nblk, int lb, uint32_t* __restrict__ btot) {
+    depth_count_body(keys, N, block_D, nblk, lb, btot);
+}
+
+__device__ __forceinline__ void depth_scatter_body(const uint32_t* __restrict__ keys, int N, const uint32_t* __restrict__ block_D, int nblk, int lb,
                 const uint32_t* __restrict__ btot, uint32_t* __restrict__ bcur, uint32_t* __restrict__ gpos, uint32_t* __restrict__ gmap,
                 uint32_t* __restrict__ drange, unsigned long long* __restrict__ pair_out) {
     __shared__ uint32_t s_hist[DS_NB_MAX + 1];          // this block's counts, then its next free slot per bin
@@ -370,6 +390,13 @@ k_depth_scatter(const uint32_t* __restrict__ keys, int N, const uint32_t* __rest
         const int i = base + tid + u * DS_THREADS;
         if (i < N) { const uint32_t p = atomicAdd(&s_hist[depth_bin(kk[u], r)], 1u); pair_out[p] = ((unsigned long long)kk[u] << 32) | (unsigned long long)(uint32_t)i; }
     }
+}
+
+__global__ void __launch_bounds__(DS_THREADS)
+k_depth_scatter(const uint32_t* __restrict__ keys, int N, const uint32_t* __restrict__ block_D, int nblk, int lb,
+                const uint32_t* __restrict__ btot, uint32_t* __restrict__ bcur, uint32_t* __restrict__ gpos, uint32_t* __restrict__ gmap,
+                uint32_t* __restrict__ drange, unsigned long long* __restrict__ pair_out) {
+    depth_scatter_body(keys, N, block_D, nblk, lb, btot, bcur, gpos, gmap, drange, pair_out);
 }
 
 // loads that must see what this wave (or another) wrote to global memory earlier (the fallback's ping-pong passes, the last wave's scan)
@@ -509,8 +536,7 @@ __device__ __forceinline__ uint32_t group_sort_regs(const unsigned long long* __
     return total;
 }
 
-__global__ void __launch_bounds__(DS_THREADS)
-k_depth_group_sort(int N, const uint32_t* __restrict__ gpos, const uint32_t* __restrict__ drange,
+__device__ __forceinline__ void depth_group_sort_body(int N, const uint32_t* __restrict__ gpos, const uint32_t* __restrict__ drange,
                    unsigned long long* pair_a, uint32_t* key_b, uint32_t* val_b,
                    const uint32_t* __restrict__ tiles_touched, uint32_t* __restrict__ offs_rank, uint32_t* __restrict__ bsum, int gmax) {
     __shared__ unsigned long long s_pair[DS_CAP];          // 16 KB: the cross-wave exchanges (the fallback's digit table aliases it)
@@ -632,10 +658,16 @@ k_depth_group_sort(int N, const uint32_t* __restrict__ gpos, const uint32_t* __r
     if (tid == 0) bsum[b] = total;          // the group's tile sum; K3 scans them
 }
 
+__global__ void __launch_bounds__(DS_THREADS)
+k_depth_group_sort(int N, const uint32_t* __restrict__ gpos, const uint32_t* __restrict__ drange,
+                   unsigned long long* pair_a, uint32_t* key_b, uint32_t* val_b,
+                   const uint32_t* __restrict__ tiles_touched, uint32_t* __restrict__ offs_rank, uint32_t* __restrict__ bsum, int gmax) {
+    depth_group_sort_body(N, gpos, drange, pair_a, key_b, val_b, tiles_touched, offs_rank, bsum, gmax);
+}
+
 // exclusive scan, in place, of the groups' tile sums (one workgroup; <= DS_NB_MAX + 1 values): only for N beyond DS_FUSED_GROUPS
 // groups, see k_duplicate
-__global__ void __launch_bounds__(1024)
-k_depth_prefix(const uint32_t* __restrict__ drange, uint32_t* __restrict__ bsum) {
+__device__ __forceinline__ void depth_prefix_body(const uint32_t* __restrict__ drange, uint32_t* __restrict__ bsum) {
     __shared__ uint32_t s_w[16];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int nb1 = (int)drange[DR_GROUPS] + 1;
@@ -654,6 +686,9 @@ k_depth_prefix(const uint32_t* __restrict__ drange, uint32_t* __restrict__ bsum)
     for (int k = 0; k < 9; ++k) { const int q = tid * per + k; if (k < per && q < nb1) bsum[q] = run; run += v[k]; }
 }
 
+__global__ void __launch_bounds__(1024)
+k_depth_prefix(const uint32_t* __restrict__ drange, uint32_t* __restrict__ bsum) { depth_prefix_body(drange, bsum); }
+
 // K3: one thread per depth rank; emits that Gaussian's instances, element = (tile << 32) | rank, at offs_rank[rank]...
 // loc_rank[rank] is the prefix INSIDE the rank's sort group (k_depth_group_sort, scratch); the group's own prefix (scan of bsum) is
 // added here and the sum written to offs_rank (geom->offsets = exclusive scan of tiles_touched in rank order is an output of the
@@ -662,8 +697,7 @@ k_depth_prefix(const uint32_t* __restrict__ drange, uint32_t* __restrict__ bsum)
 // PRE: `bsum` already holds the exclusive scan of the groups' tile sums (k_depth_prefix: large N, where every workgroup redoing
 // the scan is N^2 / 40 960 loads) -- otherwise the workgroup scans the <= 2 049 sums itself (cheaper than a launch).
 template <bool PRE>
-__global__ void __launch_bounds__(TG_BLOCK)
-k_duplicate(int N, int tiles_x, int T, const uint32_t* __restrict__ id_rank, const uint32_t* __restrict__ key_rank,
+__device__ __forceinline__ void duplicate_body(int N, int tiles_x, int T, const uint32_t* __restrict__ id_rank, const uint32_t* __restrict__ key_rank,
             const uint32_t* __restrict__ loc_rank, uint32_t* __restrict__ offs_rank, const uint32_t* __restrict__ drange, const uint32_t* __restrict__ gmap, const uint32_t* __restrict__ bsum,
             const uint32_t* __restrict__ tiles_touched, const uint2* __restrict__ rect, uint64_t* __restrict__ elems,
             uint2* __restrict__ ranges, uint32_t* __restrict__ zero_words, int num_zero_words) {
@@ -708,9 +742,18 @@ k_duplicate(int N, int tiles_x, int T, const uint32_t* __restrict__ id_rank, con
             elems[off++] = ((uint64_t)(y * (uint32_t)tiles_x + x) << 32) | (uint64_t)(uint32_t)r;
 }
 
-// K5: ranges[tile] = [first, last) by boundary detection on the sorted keys' high word (K3 zero-filled `ranges`).
+template <bool PRE>
 __global__ void __launch_bounds__(TG_BLOCK)
-k_ranges(uint32_t D, const uint64_t* __restrict__ keys, uint2* __restrict__ ranges) {
+k_duplicate(int N, int tiles_x, int T, const uint32_t* __restrict__ id_rank, const uint32_t* __restrict__ key_rank,
+            const uint32_t* __restrict__ loc_rank, uint32_t* __restrict__ offs_rank, const uint32_t* __restrict__ drange, const uint32_t* __restrict__ gmap, const uint32_t* __restrict__ bsum,
+            const uint32_t* __restrict__ tiles_touched, const uint2* __restrict__ rect, uint64_t* __restrict__ elems,
+            uint2* __restrict__ ranges, uint32_t* __restrict__ zero_words, int num_zero_words) {
+    duplicate_body<PRE>(N, tiles_x, T, id_rank, key_rank, loc_rank, offs_rank, drange, gmap, bsum, tiles_touched, rect, elems, ranges,
+                        zero_words, num_zero_words);
+}
+
+// K5: ranges[tile] = [first, last) by boundary detection on the sorted keys' high word (K3 zero-filled `ranges`).
+__device__ __forceinline__ void ranges_body(uint32_t D, const uint64_t* __restrict__ keys, uint2* __restrict__ ranges) {
     const uint32_t i = blockIdx.x * TG_BLOCK + threadIdx.x;
     if (i >= D) return;
     const uint32_t cur = (uint32_t)(keys[i] >> 32);
@@ -722,10 +765,12 @@ k_ranges(uint32_t D, const uint64_t* __restrict__ keys, uint2* __restrict__ rang
     if (i == D - 1) ranges[cur].y = D;
 }
 
+__global__ void __launch_bounds__(TG_BLOCK)
+k_ranges(uint32_t D, const uint64_t* __restrict__ keys, uint2* __restrict__ ranges) { ranges_body(D, keys, ranges); }
+
 // Launch order of the blend kernels: longest tile list first (LPT), as a counting sort on a 1024-level log-ish length
 // bucket in ONE workgroup (speed only: any order is correct; ties keep no particular order).
-__global__ void __launch_bounds__(1024)
-k_tile_order(uint32_t T, const uint2* __restrict__ ranges, uint32_t* __restrict__ order, uint32_t* __restrict__ zero_words,
+__device__ __forceinline__ void tile_order_body(uint32_t T, const uint2* __restrict__ ranges, uint32_t* __restrict__ order, uint32_t* __restrict__ zero_words,
              int num_zero_words) {
     __shared__ uint32_t s_cnt[1024];
     __shared__ uint32_t s_w[16];
@@ -759,12 +804,18 @@ k_tile_order(uint32_t T, const uint2* __restrict__ ranges, uint32_t* __restrict_
     }
 }
 
+__global__ void __launch_bounds__(1024)
+k_tile_order(uint32_t T, const uint2* __restrict__ ranges, uint32_t* __restrict__ order, uint32_t* __restrict__ zero_words,
+             int num_zero_words) {
+    tile_order_body(T, ranges, order, zero_words, num_zero_words);
+}
+
 inline int tile_bits(uint32_t T) {
     int bits = 0;
     while ((1u << bits) < T && bits < 31) ++bits;     // ceil(log2 T)
     return bits == 0 ? 1 : bits;
 }
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+__host__ __device__ inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // ---- scratch layouts ------------------------------------------------------------------------------------------------
 // scan_temp (Gaussian level, sized by scan_temp_bytes(N)):
@@ -784,9 +835,9 @@ struct GaussScratch {
                                    // group's prefix and writes geom->offsets -- from this read-only source, so K3 can run again
     size_t header_bytes;
 };
-inline size_t zero_header_bytes(int passes, size_t extra) { return align256((size_t)passes * RS_ZERO_WORDS * 4 + extra); }
-inline size_t depth_header_bytes() { return align256(((size_t)2 * (DS_NB_MAX + 1) + 2) * 4); }
-inline GaussScratch gauss_scratch(void* base, int N) {
+__host__ __device__ inline size_t zero_header_bytes(int passes, size_t extra) { return align256((size_t)passes * RS_ZERO_WORDS * 4 + extra); }
+__host__ __device__ inline size_t depth_header_bytes() { return align256(((size_t)2 * (DS_NB_MAX + 1) + 2) * 4); }
+__host__ __device__ inline GaussScratch gauss_scratch(void* base, int N) {
     GaussScratch g;
     char* p = (char*)base;
     g.header_bytes = depth_header_bytes();
@@ -805,13 +856,13 @@ inline GaussScratch gauss_scratch(void* base, int N) {
     return g;
 }
 // pass `pass` of `passes`: its gtable sits in the zeroed header at `base`, its table after the header
-inline RadixTables tables_at(uint32_t* base, int pass, int passes, size_t extra) {
+__host__ __device__ inline RadixTables tables_at(uint32_t* base, int pass, int passes, size_t extra) {
     RadixTables t;
     t.gtable = base + (size_t)pass * RS_ZERO_WORDS;
     t.table = reinterpret_cast<uint32_t*>((char*)base + zero_header_bytes(passes, extra)) + (size_t)pass * RS_MAX_BLOCKS * 256;
     return t;
 }
-inline void pass_geometry(uint32_t n, uint32_t& blocks, uint32_t& per) {
+__host__ __device__ inline void pass_geometry(uint32_t n, uint32_t& blocks, uint32_t& per) {
     per = ((n + RS_MAX_BLOCKS - 1) / RS_MAX_BLOCKS + 63u) & ~63u;       // elements per block, multiple of 64
     if (per < RS_PER_MIN) per = RS_PER_MIN;
     blocks = (n + per - 1) / per;
@@ -827,7 +878,7 @@ size_t scan_temp_bytes(int N) {
 }
 
 constexpr int TILE_PASSES_MAX = 3;      // tile ids up to 2^24 in digits of at most 8 bits (the count / scatter kernels index 256-entry LDS tables)
-inline size_t sort_tables_bytes() {
+__host__ __device__ inline size_t sort_tables_bytes() {
     return zero_header_bytes(TILE_PASSES_MAX, 0) + align256(TILE_PASSES_MAX * (size_t)RS_MAX_BLOCKS * 256 * 4);
 }
 size_t sort_temp_bytes(uint32_t D, uint32_t T) {
@@ -840,6 +891,197 @@ uint32_t* bin_header_ptr(const TexGSGeom* g, int N, int* words) {       // bin t
     const GaussScratch gs = gauss_scratch(g->scan_temp, N);
     *words = (int)(gs.header_bytes / 4);
     return gs.btot;
+}
+
+// ---- the batched front end (texgs_multiview.h): K2 .. K5 of the views of one multi-view step, the view as blockIdx.y ---------------
+// Every `*_views` kernel picks its view's pointers out of a by-value table and runs the single-view kernel's body: per view the same
+// blocks do the same work on the same scratch layout, so each view's lists are those of the per-view launches, bit for bit.  A launch
+// then holds V times the blocks: 300 k Gaussians or 1.1 M instances cannot fill the chip (profiles/HISTORY.md findings 17, 24), eight
+// views' worth come closer, and eleven dependent launches per VIEW become eleven per STEP.  The views' instance counts differ: the
+// grid is sized for the largest, a view's surplus blocks return at once.
+namespace {
+
+struct BinView {            // one view's buffers (TexGSGeom / TexGSBinning fields) and its instance count
+    const uint32_t* depth;
+    const uint32_t* tiles_touched;
+    const uint2* rect;
+    uint32_t* offsets;
+    void* scan_temp;
+    uint64_t *keys_unsorted, *keys_sorted;
+    uint32_t* point_list;
+    uint2* ranges;
+    uint32_t* tile_order;
+    void* sort_temp;
+    uint32_t* zero_words;   // TexGSImage.tex_bin_count (k_tile_order zero-fills it), or NULL
+    uint32_t D;
+};
+struct BinViews { BinView v[TEXGS_BATCH_MAX_VIEWS]; };
+
+__device__ __forceinline__ uint64_t* sort_tmp_of(const BinView& w) { return reinterpret_cast<uint64_t*>((char*)w.sort_temp + sort_tables_bytes()); }
+
+__global__ void __launch_bounds__(DS_THREADS)
+k_depth_count_views(BinViews a, int N, int nblk, int lb) {
+    const BinView& w = a.v[blockIdx.y];
+    const GaussScratch gs = gauss_scratch(w.scan_temp, N);
+    depth_count_body(w.depth, N, gs.block_D, nblk, lb, gs.btot);
+}
+
+__global__ void __launch_bounds__(DS_THREADS)
+k_depth_scatter_views(BinViews a, int N, int nblk, int lb) {
+    const BinView& w = a.v[blockIdx.y];
+    const GaussScratch gs = gauss_scratch(w.scan_temp, N);
+    depth_scatter_body(w.depth, N, gs.block_D, nblk, lb, gs.btot, gs.bcur, gs.gpos, gs.gmap, gs.drange, gs.pair_a);
+}
+
+__global__ void __launch_bounds__(DS_THREADS)
+k_depth_group_sort_views(BinViews a, int N, int gmax) {
+    const BinView& w = a.v[blockIdx.y];
+    const GaussScratch gs = gauss_scratch(w.scan_temp, N);
+    depth_group_sort_body(N, gs.gpos, gs.drange, gs.pair_a, gs.key_b, gs.val_b, w.tiles_touched, gs.loc_b, gs.bsum, gmax);
+}
+
+__global__ void __launch_bounds__(1024)
+k_depth_prefix_views(BinViews a, int N) {
+    const GaussScratch gs = gauss_scratch(a.v[blockIdx.y].scan_temp, N);
+    depth_prefix_body(gs.drange, gs.bsum);
+}
+
+template <bool PRE>
+__global__ void __launch_bounds__(TG_BLOCK)
+k_duplicate_views(BinViews a, int N, int tiles_x, int T, int num_zero_words) {
+    const BinView& w = a.v[blockIdx.y];
+    if (w.D == 0u) {        // a view without instances: no K3 / K4 (as in the per-view path, which memsets), every tile's range is empty
+        for (int k = blockIdx.x * TG_BLOCK + threadIdx.x; k < T; k += (int)gridDim.x * TG_BLOCK) w.ranges[k] = make_uint2(0u, 0u);
+        return;
+    }
+    const GaussScratch gs = gauss_scratch(w.scan_temp, N);
+    duplicate_body<PRE>(N, tiles_x, T, gs.val_b, gs.key_b, gs.loc_b, w.offsets, gs.drange, gs.gmap, gs.bsum, w.tiles_touched, w.rect,
+                        w.keys_unsorted, w.ranges, reinterpret_cast<uint32_t*>(w.sort_temp), num_zero_words);
+}
+
+// `from_tmp` / `to_tmp`: the pass reads / writes the ping-pong buffer in sort_temp instead of keys_unsorted (launch_sort's `src` / `dst`)
+__global__ void __launch_bounds__(RS_THREADS)
+k_radix_count_views(BinViews a, int pass, int from_tmp, int shift, uint32_t mask) {
+    const BinView& w = a.v[blockIdx.y];
+    uint32_t blocks, per;
+    pass_geometry(w.D, blocks, per);
+    if (w.D == 0u || blockIdx.x >= blocks) return;
+    radix_count_body<uint64_t>(from_tmp ? sort_tmp_of(w) : w.keys_unsorted, w.D, per, shift, mask,
+                               tables_at(reinterpret_cast<uint32_t*>(w.sort_temp), pass, TILE_PASSES_MAX, 0));
+}
+
+template <int MODE>
+__global__ void __launch_bounds__(RS_THREADS)
+k_radix_scatter_views(BinViews a, int N, int pass, int from_tmp, int to_tmp, int shift, uint32_t mask, int bits) {
+    const BinView& w = a.v[blockIdx.y];
+    uint32_t blocks, per;
+    pass_geometry(w.D, blocks, per);
+    if (w.D == 0u || blockIdx.x >= blocks) return;
+    const uint64_t* src = from_tmp ? sort_tmp_of(w) : w.keys_unsorted;
+    const RadixTables t = tables_at(reinterpret_cast<uint32_t*>(w.sort_temp), pass, TILE_PASSES_MAX, 0);
+    if (MODE == 2) {
+        const GaussScratch gs = gauss_scratch(w.scan_temp, N);
+        radix_scatter_body<uint64_t, 2>(src, nullptr, w.keys_sorted, w.point_list, w.D, blocks, per, shift, mask, bits, t, gs.key_b, gs.val_b);
+    } else {
+        radix_scatter_body<uint64_t, 1>(src, nullptr, to_tmp ? sort_tmp_of(w) : w.keys_unsorted, nullptr, w.D, blocks, per, shift, mask, bits, t,
+                                        nullptr, nullptr);
+    }
+}
+
+__global__ void __launch_bounds__(TG_BLOCK)
+k_ranges_views(BinViews a) {
+    const BinView& w = a.v[blockIdx.y];
+    if (w.D != 0u) ranges_body(w.D, w.keys_sorted, w.ranges);
+}
+
+__global__ void __launch_bounds__(1024)
+k_tile_order_views(BinViews a, uint32_t T, int num_zero_words) {
+    const BinView& w = a.v[blockIdx.y];
+    tile_order_body(T, w.ranges, w.tile_order, w.zero_words, w.zero_words ? num_zero_words : 0);
+}
+
+BinViews bin_views(const TexGSGeom* g, const TexGSBinning* b, const TexGSImage* img, int count) {
+    BinViews a;
+    memset(&a, 0, sizeof(a));
+    for (int v = 0; v < count; ++v) {
+        BinView& w = a.v[v];
+        w.depth = reinterpret_cast<const uint32_t*>(g[v].depth); w.tiles_touched = g[v].tiles_touched;
+        w.rect = reinterpret_cast<const uint2*>(g[v].rect); w.offsets = g[v].offsets; w.scan_temp = g[v].scan_temp;
+        if (b) {
+            w.keys_unsorted = b[v].keys_unsorted; w.keys_sorted = b[v].keys_sorted; w.point_list = b[v].point_list;
+            w.ranges = reinterpret_cast<uint2*>(b[v].ranges); w.tile_order = b[v].tile_order; w.sort_temp = b[v].sort_temp;
+            w.D = b[v].num_rendered;
+        }
+        if (img) w.zero_words = img[v].tex_bin_count;
+    }
+    return a;
+}
+
+}  // namespace
+
+// K2 of `count` views (launch_depth_sort_scan with the view as the grid's second dimension)
+hipError_t launch_depth_sort_scan_views(const TexGSGeom* g, int N, int count, hipStream_t s) {
+    if (N <= 0 || count <= 0) return hipSuccess;
+    const BinViews a = bin_views(g, nullptr, nullptr, count);
+    const int nblk = (N + TG_BLOCK - 1) / TG_BLOCK;
+    const int blocks = (N + DS_PER - 1) / DS_PER;
+    const int lb = depth_log2_bins(N);
+    const int gmax = depth_max_groups(N, 1 << lb);
+    hipLaunchKernelGGL(k_depth_count_views, dim3(blocks, count), dim3(DS_THREADS), 0, s, a, N, nblk, lb);
+    hipLaunchKernelGGL(k_depth_scatter_views, dim3(blocks, count), dim3(DS_THREADS), 0, s, a, N, nblk, lb);
+    hipLaunchKernelGGL(k_depth_group_sort_views, dim3(gmax + (N + (int)DS_COPY - 1) / (int)DS_COPY, count), dim3(DS_THREADS), 0, s, a, N, gmax);
+    if (gmax > DS_FUSED_GROUPS) hipLaunchKernelGGL(k_depth_prefix_views, dim3(1, count), dim3(1024), 0, s, a, N);
+    return hipGetLastError();
+}
+
+// K3, K4, K5 of `count` views of one image size (launch_duplicate, launch_sort, launch_ranges with the view as the grid's second
+// dimension); b[v].num_rendered = the view's D.  num_zero_words: the words of a view's tex_bin_count (views without one: none).
+// `stage`: TEXGS_K_DUPLICATE, TEXGS_K_SORT or TEXGS_K_RANGES -- the caller runs the three in this order, each inside the profile bracket
+// of its kernel group, as the per-view path does.
+hipError_t launch_bin_views(int stage, const CamConst& c, const TexGSGeom* g, const TexGSBinning* b, const TexGSImage* img, int count,
+                            int num_zero_words, hipStream_t s) {
+    if (c.N <= 0 || count <= 0) return hipSuccess;
+    const BinViews a = bin_views(g, b, img, count);
+    const uint32_t T = (uint32_t)(c.tiles_x * c.tiles_y);
+    uint32_t dmax = 0u;
+    for (int v = 0; v < count; ++v) dmax = b[v].num_rendered > dmax ? b[v].num_rendered : dmax;
+    const int nblocks = (c.N + TG_BLOCK - 1) / TG_BLOCK;
+    const bool pre = depth_max_groups(c.N, 1 << depth_log2_bins(c.N)) > DS_FUSED_GROUPS;
+    const int hdr = (int)(zero_header_bytes(TILE_PASSES_MAX, 0) / 4);
+    if (stage == TEXGS_K_DUPLICATE) {
+        if (pre) hipLaunchKernelGGL(k_duplicate_views<true>, dim3(nblocks, count), dim3(TG_BLOCK), 0, s, a, c.N, c.tiles_x, (int)T, hdr);
+        else hipLaunchKernelGGL(k_duplicate_views<false>, dim3(nblocks, count), dim3(TG_BLOCK), 0, s, a, c.N, c.tiles_x, (int)T, hdr);
+    }
+    if (stage == TEXGS_K_SORT && dmax > 0u) {
+        const int tb = tile_bits(T);
+        const int npass = (tb + 7) / 8;
+        if (npass > TILE_PASSES_MAX) return hipErrorInvalidValue;
+        uint32_t blocks = 1u;                           // (not monotone in D: 524 288 instances take 1024 blocks, one more 911)
+        for (int v = 0; v < count; ++v) {
+            uint32_t bv, per;
+            pass_geometry(b[v].num_rendered, bv, per);
+            blocks = bv > blocks ? bv : blocks;
+        }
+        int from_tmp = 0, shift = 32, left = tb;
+        for (int pass = 0; pass < npass; ++pass) {
+            const int bits = (left + (npass - pass) - 1) / (npass - pass);
+            const uint32_t mask = (1u << bits) - 1u;
+            hipLaunchKernelGGL(k_radix_count_views, dim3(blocks, count), dim3(RS_THREADS), 0, s, a, pass, from_tmp, shift, mask);
+            if (pass == npass - 1) {
+                hipLaunchKernelGGL(k_radix_scatter_views<2>, dim3(blocks, count), dim3(RS_THREADS), 0, s, a, c.N, pass, from_tmp, 0, shift, mask, bits);
+            } else {
+                const int to_tmp = from_tmp ? 0 : 1;
+                hipLaunchKernelGGL(k_radix_scatter_views<1>, dim3(blocks, count), dim3(RS_THREADS), 0, s, a, c.N, pass, from_tmp, to_tmp, shift, mask, bits);
+                from_tmp = to_tmp;
+            }
+            shift += bits; left -= bits;
+        }
+    }
+    if (stage == TEXGS_K_RANGES) {
+        if (dmax > 0u) hipLaunchKernelGGL(k_ranges_views, dim3((dmax + TG_BLOCK - 1) / TG_BLOCK, count), dim3(TG_BLOCK), 0, s, a);
+        hipLaunchKernelGGL(k_tile_order_views, dim3(1, count), dim3(1024), 0, s, a, T, num_zero_words);
+    }
+    return hipGetLastError();
 }
 
 // Gaussian level: depth sort + exclusive scan of tiles_touched in rank order (three launches, see above).  Needs K1's depth keys

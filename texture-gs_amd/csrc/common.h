@@ -85,6 +85,11 @@ size_t sort_temp_bytes(uint32_t D, uint32_t T);
 hipError_t launch_duplicate(const CamConst& c, const TexGSGeom* g, TexGSBinning* b, hipStream_t s);
 hipError_t launch_sort(const CamConst& c, const TexGSGeom* g, TexGSBinning* b, hipStream_t s);
 hipError_t launch_ranges(const CamConst& c, TexGSBinning* b, uint32_t* zero_words, int num_zero_words, hipStream_t s);
+// the batched front end (texgs_multiview.h): arrays of `count` views, validated by the caller (abi.hip)
+hipError_t launch_preprocess_fwd_views(const TexGSFrame* f, const TexGSInputs* in, TexGSGeom* g, int count, uint32_t* sums, hipStream_t s);
+hipError_t launch_depth_sort_scan_views(const TexGSGeom* g, int N, int count, hipStream_t s);
+hipError_t launch_bin_views(int stage, const CamConst& c, const TexGSGeom* g, const TexGSBinning* b, const TexGSImage* img, int count,
+                            int num_zero_words, hipStream_t s);
 hipError_t launch_render_fwd(const CamConst& c, const TexGSFrame* f, const TexGSInputs* in, const TexGSGeom* g,
                        const TexGSBinning* b, TexGSImage* img, hipStream_t s);
 size_t tex_bin_count(int R);

@@ -8,6 +8,7 @@
 // One thread per Gaussian, 256 threads (4 wave64) per workgroup.  HBM-bound: reads 92+12K B, writes a 32-B test record
 // + an 80-B shading record + 24 B of SoA state per Gaussian.
 #include "common.h"
+#include <cstring>
 
 namespace {
 
@@ -336,17 +337,27 @@ __device__ __forceinline__ void sh_rows_out(float* __restrict__ g, const float* 
 }
 
 // ------------------------------------------------------------------------------------------------ K1
-template <bool COV>
-__global__ void __launch_bounds__(TG_BLOCK)
-k_preprocess_fwd(CamConst C, const float* __restrict__ vm, const float* __restrict__ pm, const float* __restrict__ cp,
+// The block-cooperative, contiguous read of a workgroup's SH rows into LDS (180 B per Gaussian at K = 15); ends in a barrier
+__device__ __forceinline__ void k1_stage_sh(const CamConst& C, const float* __restrict__ shs, float* s_sh) {
+    const int row = 3 * C.sh_coeffs;
+    const size_t first = (size_t)blockIdx.x * TG_BLOCK * row;
+    const size_t total = (size_t)C.N * row;
+    const int count = (int)min((size_t)TG_BLOCK * row, total - first);
+    for (int k = threadIdx.x; k < count; k += TG_BLOCK) s_sh[k] = shs[first + k];
+    __syncthreads();
+}
+
+// K1 of ONE view for this workgroup's 256 Gaussians: the whole kernel body.  VIEWS = false: k_preprocess_fwd, which stages the SH rows
+// between the projection and the colour (the code it always was).  VIEWS = true: k_preprocess_fwd_views, which staged them once in
+// front of its loop over the views and also wants the three partial sums of the readback in `sums_out` (one array for all views).
+template <bool COV, bool VIEWS>
+__device__ __forceinline__ void k1_view(const CamConst& C, const float* __restrict__ vm, const float* __restrict__ pm, const float* __restrict__ cp,
                  const float* __restrict__ means, const float* __restrict__ shs, const float* __restrict__ opac,
                  const float* __restrict__ scales, const float* __restrict__ rots, const float* __restrict__ uvs,
                  const float* __restrict__ juv, const float* __restrict__ coff, const float* __restrict__ cov6,
                  float4* __restrict__ rec_test, float4* __restrict__ rec_shade, float* __restrict__ depth, int32_t* __restrict__ radii,
                  uint2* __restrict__ rect, uint32_t* __restrict__ tiles_touched, uint32_t* __restrict__ block_D,
-                 uint32_t* __restrict__ zero_words, int num_zero_words) {
-    extern __shared__ __attribute__((aligned(16))) float s_sh[];          // [256][3K] staged SH rows (coalesced load)
-    __shared__ uint32_t s_tt[5 * (TG_BLOCK / 64)];
+                 uint32_t* __restrict__ zero_words, int num_zero_words, uint32_t* __restrict__ sums_out, float* s_sh, uint32_t* s_tt) {
     const int i = blockIdx.x * TG_BLOCK + threadIdx.x;
     const bool live = i < C.N;
     for (int k = i; k < num_zero_words; k += (int)gridDim.x * TG_BLOCK) zero_words[k] = 0u;      // count tables of the depth sort (K2)
@@ -361,12 +372,8 @@ k_preprocess_fwd(CamConst C, const float* __restrict__ vm, const float* __restri
     }
     const int na = (shs != nullptr && C.sh_degree > 0) ? sh_active(C.sh_degree, C.sh_coeffs) : 0;
     const int row = 3 * C.sh_coeffs;
-    if (na > 0) {           // block-cooperative, contiguous read of this block's SH rows (180 B per Gaussian at K = 15)
-        const size_t first = (size_t)blockIdx.x * TG_BLOCK * row;
-        const size_t total = (size_t)C.N * row;
-        const int count = (int)min((size_t)TG_BLOCK * row, total - first);
-        for (int k = threadIdx.x; k < count; k += TG_BLOCK) s_sh[k] = shs[first + k];
-        __syncthreads();
+    if constexpr (!VIEWS) {
+        if (na > 0) k1_stage_sh(C, shs, s_sh);
     }
     // Two things leave this kernel as one partial sum per workgroup (no atomics, nothing to zero; the host reads them back while
     // the depth sort runs and adds them up): D = sum of tiles_touched, and a 64-bit FINGERPRINT of what the tile binning, K6's
@@ -460,6 +467,64 @@ k_preprocess_fwd(CamConst C, const float* __restrict__ vm, const float* __restri
             r = (threadIdx.x < 3) ? r + v : ((threadIdx.x == 3) ? min(r, v) : max(r, v));
         }
         block_D[threadIdx.x * gridDim.x + blockIdx.x] = r;  // five arrays of gridDim.x: tiles_touched, fingerprint lo, hi, min / max valid depth key
+        if constexpr (VIEWS) {
+            if (threadIdx.x < 3) sums_out[threadIdx.x * gridDim.x + blockIdx.x] = r;      // the readback's three, all views in one array
+        }
+    }
+}
+
+template <bool COV>
+__global__ void __launch_bounds__(TG_BLOCK)
+k_preprocess_fwd(CamConst C, const float* __restrict__ vm, const float* __restrict__ pm, const float* __restrict__ cp,
+                 const float* __restrict__ means, const float* __restrict__ shs, const float* __restrict__ opac,
+                 const float* __restrict__ scales, const float* __restrict__ rots, const float* __restrict__ uvs,
+                 const float* __restrict__ juv, const float* __restrict__ coff, const float* __restrict__ cov6,
+                 float4* __restrict__ rec_test, float4* __restrict__ rec_shade, float* __restrict__ depth, int32_t* __restrict__ radii,
+                 uint2* __restrict__ rect, uint32_t* __restrict__ tiles_touched, uint32_t* __restrict__ block_D,
+                 uint32_t* __restrict__ zero_words, int num_zero_words) {
+    extern __shared__ __attribute__((aligned(16))) float s_sh[];          // [256][3K] staged SH rows (coalesced load)
+    __shared__ uint32_t s_tt[5 * (TG_BLOCK / 64)];
+    k1_view<COV, false>(C, vm, pm, cp, means, shs, opac, scales, rots, uvs, juv, coff, cov6, rec_test, rec_shade, depth, radii, rect,
+                        tiles_touched, block_D, zero_words, num_zero_words, nullptr, s_sh, s_tt);
+}
+
+// K1 of the V views of one multi-view step (texgs_preprocess_forward_views): same Gaussians, same image size and sh_degree, V cameras.
+// The workgroup stages its SH rows once -- 180 of the 272 B a Gaussian's inputs take at K = 15 -- and walks the views; the other per-Gaussian
+// inputs are read again per view, from the cache lines the first view brought in.  Every view runs k1_view, the single-view kernel's own
+// body, on its own camera and output pointers: its outputs are that kernel's, bit for bit.  The views travel by value in the kernel
+// arguments (wave-uniform loads), as k_sh_flush's records do.
+struct K1View {
+    CamConst C;
+    const float *vm, *pm, *cp;
+    float4 *rec_test, *rec_shade;
+    float* depth;
+    int32_t* radii;
+    uint2* rect;
+    uint32_t *tiles_touched, *block_D, *zero_words;
+};
+struct K1Views {
+    K1View v[TEXGS_BATCH_MAX_VIEWS];
+    int32_t count;
+};
+
+template <bool COV>
+__global__ void __launch_bounds__(TG_BLOCK)
+k_preprocess_fwd_views(K1Views a, const float* __restrict__ means, const float* __restrict__ shs, const float* __restrict__ opac,
+                       const float* __restrict__ scales, const float* __restrict__ rots, const float* __restrict__ uvs,
+                       const float* __restrict__ juv, const float* __restrict__ coff, const float* __restrict__ cov6,
+                       int num_zero_words, uint32_t* __restrict__ sums, int sums_stride) {
+    extern __shared__ __attribute__((aligned(16))) float s_sh[];
+    __shared__ uint32_t s_tt[5 * (TG_BLOCK / 64)];
+    {
+        const CamConst& C0 = a.v[0].C;          // (N, sh_degree and sh_coeffs are the same in every view: checked by the caller)
+        if (shs != nullptr && C0.sh_degree > 0 && sh_active(C0.sh_degree, C0.sh_coeffs) > 0) k1_stage_sh(C0, shs, s_sh);
+    }
+#pragma unroll 1
+    for (int v = 0; v < a.count; ++v) {
+        const K1View& w = a.v[v];
+        k1_view<COV, true>(w.C, w.vm, w.pm, w.cp, means, shs, opac, scales, rots, uvs, juv, coff, cov6, w.rec_test, w.rec_shade, w.depth,
+                           w.radii, w.rect, w.tiles_touched, w.block_D, w.zero_words, num_zero_words, sums + (size_t)v * sums_stride, s_sh, s_tt);
+        __syncthreads();                        // s_tt is the next view's too
     }
 }
 
@@ -818,6 +883,33 @@ hipError_t launch_preprocess_fwd(const CamConst& c, const TexGSFrame* f, const T
                        reinterpret_cast<uint2*>(g->rect), g->tiles_touched, bin_block_sums_ptr(g, c.N), hdr, hdr_words)
     if (in->cov3D_precomp) K1_LAUNCH(true); else K1_LAUNCH(false);
 #undef K1_LAUNCH
+    return hipGetLastError();
+}
+
+// `count` <= TEXGS_BATCH_MAX_VIEWS views of equal N, image size, sh_degree and sh_coeffs (checked by the caller, abi.hip); `sums`:
+// device u32[count][3 * ceil(N / 256)]
+hipError_t launch_preprocess_fwd_views(const TexGSFrame* f, const TexGSInputs* in, TexGSGeom* g, int count, uint32_t* sums, hipStream_t s) {
+    const CamConst c0 = make_cam(&f[0]);
+    if (c0.N <= 0 || count <= 0) return hipSuccess;
+    const int blocks = (c0.N + TG_BLOCK - 1) / TG_BLOCK;
+    const size_t lds = (in->shs && c0.sh_degree > 0) ? (size_t)TG_BLOCK * 3 * c0.sh_coeffs * sizeof(float) : 0;
+    K1Views a;
+    memset(&a, 0, sizeof(a));
+    a.count = count;
+    int hdr_words = 0;
+    for (int v = 0; v < count; ++v) {
+        K1View& w = a.v[v];
+        w.C = make_cam(&f[v]);
+        w.vm = f[v].viewmatrix; w.pm = f[v].projmatrix; w.cp = f[v].campos;
+        w.rec_test = reinterpret_cast<float4*>(g[v].rec_test); w.rec_shade = reinterpret_cast<float4*>(g[v].rec_shade);
+        w.depth = g[v].depth; w.radii = g[v].radii; w.rect = reinterpret_cast<uint2*>(g[v].rect); w.tiles_touched = g[v].tiles_touched;
+        w.block_D = bin_block_sums_ptr(&g[v], c0.N);
+        w.zero_words = bin_header_ptr(&g[v], c0.N, &hdr_words);
+    }
+#define K1V_LAUNCH(COV) hipLaunchKernelGGL(k_preprocess_fwd_views<COV>, dim3(blocks), dim3(TG_BLOCK), lds, s, a, in->means3D, in->shs, in->opacities, \
+                       in->scales, in->rotations, in->uvs, in->gradient_uvs, in->color_offset, in->cov3D_precomp, hdr_words, sums, 3 * blocks)
+    if (in->cov3D_precomp) K1V_LAUNCH(true); else K1V_LAUNCH(false);
+#undef K1V_LAUNCH
     return hipGetLastError();
 }
 

@@ -11,6 +11,7 @@ end-of-step work --, the per-Gaussian gradients after the last K8; the compute s
 gradients are read (GradBucket.wait).  Views are dealt to ranks by estimated cost (lpt_shard_views), not round-robin:
 the step ends with the slowest rank.
 """
+import contextlib
 import ctypes as C
 from typing import List, Sequence
 
@@ -44,6 +45,44 @@ def sh_flush_entry():
         fn.restype, fn.argtypes = SH_FLUSH_SIGNATURE
         _sh_flush_fn = fn
     return _sh_flush_fn
+
+
+BATCH_MAX_VIEWS = 16            # TEXGS_BATCH_MAX_VIEWS: views of one batched front end (K1..K5 once per step, texgs.rasterizer.batched_prefetch)
+
+
+def views_signatures():
+    """name -> (restype, argtypes) of the batched front end's entry points (include/texgs_multiview.h), in the header's order; the structs
+    are texgs.h's, passed as arrays of `count` elements"""
+    from . import _lib
+    P, vp, i32 = C.POINTER, C.c_void_p, C.c_int32
+    return {
+        "texgs_preprocess_forward_views": (C.c_int, [P(_lib.Frame), P(_lib.Inputs), P(_lib.Geom), i32, vp, vp]),
+        "texgs_depth_sort_scan_views": (C.c_int, [P(_lib.Geom), i32, i32, vp]),
+        "texgs_bin_sort_views": (C.c_int, [P(_lib.Frame), P(_lib.Geom), P(_lib.Binning), P(_lib.Image), i32, vp]),
+        "texgs_render_forward_binned": (C.c_int, [P(_lib.Frame), P(_lib.Inputs), P(_lib.Geom), P(_lib.Binning), P(_lib.Image), vp]),
+    }
+
+
+_views_fns = None
+
+
+def views_entries():
+    """The batched front end's entry points of the loaded library with their signatures applied (on first use), by name without `texgs_`"""
+    global _views_fns
+    if _views_fns is None:
+        from types import SimpleNamespace
+        from . import _lib
+        lib = _lib.load()
+        fns = {}
+        for name, (restype, argtypes) in views_signatures().items():
+            if not hasattr(lib, name):
+                raise RuntimeError(f"libtexgs.so at {_lib.LIB_PATH} does not export {name}; rebuild it with "
+                                   "`python texture-gs_amd/build.py`")
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = restype, argtypes
+            fns[name[len("texgs_"):]] = fn
+        _views_fns = SimpleNamespace(**fns)
+    return _views_fns
 
 
 def shard_views(num_views: int, rank: int, world: int) -> List[int]:
@@ -399,8 +438,26 @@ class ViewPipeline:
         except Exception:
             pass
 
+    def _prefetch_batched(self, views, prefetch_fn, stream_of, batch):
+        """The batched front end (texgs.rasterizer.batched_prefetch): prefetch_fn is called for EVERY view of the step now, under the
+        stream the view will run on, inside a batch scope -- where the rasterizer's prefetch only registers --, and the views that can
+        share K1..K5 run them once, on the current stream.  -> per view: True = nothing is left to prefetch for it; False = the caller
+        prefetches it in its usual rhythm (it fitted no group, or batching is off: `batch` false, no prefetch_fn, fewer than two views,
+        a pipeline that is not on a GPU)."""
+        if not batch or prefetch_fn is None or len(views) < 2 or self.device.type != "cuda":
+            return [False] * len(views)
+        from . import rasterizer
+        owned = []
+        with rasterizer.batched_prefetch(begin_rest=False) as scope:
+            for i, v in enumerate(views):
+                n0 = len(scope.requests)
+                with stream_of(i):
+                    prefetch_fn(v)
+                owned.append(scope.requests[n0:])
+        return [all(r.batched for r in reqs) for reqs in owned]      # (a prefetch_fn that registered nothing has done its work already)
+
     def run(self, views, forward_fn, backward_fn=None, sink=None, order="accumulate", texture_ready=None, prefetch_fn=None,
-            prefetch_ahead=1):
+            prefetch_ahead=1, batch=True):
         """`prefetch_fn(view)` (optional; e.g. GaussianRasterizer.prefetch with the arguments forward_fn will use): begins the forward
         of the view this stream renders NEXT -- K1 and the instance-count readback -- right after the current view's forward and
         BEFORE its backward is queued, so that the next forward on this stream does not wait for that backward (the first view of every
@@ -415,7 +472,12 @@ class ViewPipeline:
         order (what of view i+1 waits for view i when both add into `sink`):
         "backward"   -- its whole backward (works with any gradient path, e.g. plain autograd accumulation);
         "accumulate" -- only its accumulating kernel K8, through sink.before_accumulate (needs a GradBucket sink);
-        "none"       -- nothing: every stream accumulates into its own replica of the bucket, folded at the end."""
+        "none"       -- nothing: every stream accumulates into its own replica of the bucket, folded at the end.
+
+        `batch` (default on; needs prefetch_fn): the batched front end -- every view's forward is registered through prefetch_fn
+        BEFORE the loop and the views with the same inputs, image size and sh_degree run K1..K5 once for all of them on the caller's
+        stream (texgs.rasterizer.batched_prefetch); their forwards in the loop are K6 alone.  Views that fit no group keep the rhythm
+        above.  batch=False: every view takes the per-view path."""
         results = []
         views = list(views)
         # the deferred SH gradient of a GradBucket (a sink without these two methods is driven exactly as before)
@@ -425,9 +487,10 @@ class ViewPipeline:
             if flush_deferred is not None:
                 begin_deferred()
             try:
+                batched = self._prefetch_batched(views, prefetch_fn, lambda i: contextlib.nullcontext(), batch)
                 for i, v in enumerate(views):
                     obj = forward_fn(v)
-                    if prefetch_fn is not None and i + 1 < len(views):
+                    if prefetch_fn is not None and i + 1 < len(views) and not batched[i + 1]:
                         prefetch_fn(views[i + 1])
                     if backward_fn is not None:
                         if texture_ready is not None and sink is not None and i == len(views) - 1:
@@ -449,17 +512,20 @@ class ViewPipeline:
         cur = torch.cuda.current_stream(self.device)
         if flush_deferred is not None:
             begin_deferred(early_flush=order != "none")
-        for s in self.streams:
-            s.wait_stream(cur)
         prev_bwd = None
         render_done = {}                            # stream index -> event after that stream's latest K7 + texture-gradient reduce
         depth = len(self.streams)
         try:
+            # the batched front end: K1..K5 of every view that can share them, once, on the caller's stream, before the streams fork
+            batched = self._prefetch_batched(views, prefetch_fn, lambda i: torch.cuda.stream(self.streams[i % depth]), batch)
+            for s in self.streams:
+                s.wait_stream(cur)
             ahead = depth * max(1, int(prefetch_ahead))     # (views; prefetch_ahead = forwards begun ahead PER STREAM)
             if prefetch_fn is not None:
                 for i, v in enumerate(views[:ahead]):
-                    with torch.cuda.stream(self.streams[i % depth]):
-                        prefetch_fn(v)
+                    if not batched[i]:
+                        with torch.cuda.stream(self.streams[i % depth]):
+                            prefetch_fn(v)
             for i, v in enumerate(views):
                 k = i % depth
                 s = self.streams[k]
@@ -467,7 +533,7 @@ class ViewPipeline:
                     if order == "none":
                         sink.select(k)
                     obj = forward_fn(v)
-                    if prefetch_fn is not None and i + ahead < len(views):
+                    if prefetch_fn is not None and i + ahead < len(views) and not batched[i + ahead]:
                         prefetch_fn(views[i + ahead])
                     if backward_fn is not None:
                         if order == "backward" and prev_bwd is not None:

@@ -9,6 +9,7 @@ import ctypes as C
 import math
 import os as _os
 import threading as _threading
+import weakref as _weakref
 from collections import namedtuple
 from types import SimpleNamespace
 from typing import NamedTuple
@@ -73,6 +74,12 @@ class _Arena:
 
     def commit(self):
         self.buf = torch.empty(max(self.size, 1), dtype=torch.uint8, device=self.device)
+
+    def place(self, step_buffer, offset):
+        """Instead of commit(): the pieces live at `offset` (a multiple of 256) of a _StepBuffer shared with other arenas, which this
+        arena keeps alive."""
+        assert offset % 256 == 0 and offset + self.size <= step_buffer.buf.numel()
+        self.buf, self.owner = step_buffer.buf[offset:offset + max(self.size, 1)], step_buffer
 
     def ptr(self, name):
         return self.buf.data_ptr() + self.specs[name][0] if name in self.specs else None
@@ -169,7 +176,26 @@ def scratch_bytes():
             total += sc.bins.nbytes()
     for e in _GEOM.values():
         total += sum(ar.buf.numel() for ar in e.arenas if ar is not None and ar.buf is not None)
-    return total
+    return total + step_buffer_bytes()
+
+
+class _StepBuffer:
+    """One device allocation that holds the K1..K5 outputs of ALL views of a batched front end (batched_prefetch): every view's arenas
+    are slices of it (_Arena.place) and keep it alive -- from the start of the step until the last of its views has run its backward
+    (or was dropped: release_scratch abandons the pending ones).  A step has two: one sized by V and N, made before K1, and one sized
+    by the sum of the views' instance counts, made when those have been read back."""
+
+    def __init__(self, nbytes, device):
+        self.buf = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=device)
+        _STEP_BUFFERS.add(self)
+
+
+_STEP_BUFFERS = _weakref.WeakSet()
+
+
+def step_buffer_bytes():
+    """Bytes of the batched front end's step buffers that are alive now (counted in scratch_bytes())"""
+    return sum(b.buf.numel() for b in list(_STEP_BUFFERS))
 
 
 class _TexBins:
@@ -234,13 +260,14 @@ class _State:
     """Everything one forward leaves behind for its backward (per call: no global scratch, two forwards may
     be alive before a backward, models/texture_gaussian3d.py:318,378,410)."""
     __slots__ = ("frame", "inputs", "geom", "bin", "img", "tensors", "args", "N", "K", "R", "H", "W", "D", "cap", "tiles",
-                 "want_counts", "lazy", "backward_ran", "shared_geometry", "serial", "__weakref__")
+                 "want_counts", "lazy", "backward_ran", "shared_geometry", "serial", "fingerprint", "__weakref__")
 
     def __init__(self, frame, inputs, geom, bin, img, tensors, args, D, cap, tiles, want_counts, lazy, shared_geometry):
         self.frame, self.inputs, self.geom, self.bin, self.img, self.tensors, self.args = frame, inputs, geom, bin, img, tensors, args
         self.N, self.K, self.R, self.H, self.W = args.N, args.K, args.R, frame.image_height, frame.image_width
         self.D, self.cap, self.tiles = D, cap, tiles
         self.want_counts, self.lazy, self.backward_ran, self.shared_geometry = want_counts, lazy, False, shared_geometry
+        self.fingerprint = None     # K1's geometry fingerprint of this forward (set by the forward; diagnostics / tests)
         with _PRED_LOCK:
             _SERIAL[0] += 1
             self.serial = _SERIAL[0]
@@ -391,6 +418,26 @@ class _Forward:
                 bool(st.debug), t(st.bg), t(st.viewmatrix), t(st.projmatrix), t(st.campos)) + tuple(t(x) for x in self.raw) + self.flags
 
     def begin(self):
+        lib = _lib.load()
+        self._plan()
+        a, N, stream = self.args, self.args.N, self.stream
+        with torch.cuda.device(a.means3D.device):
+            self.fix.commit()
+            self._bind()
+            refs = self.refs
+            _lib.call(lib.texgs_preprocess_forward, *refs, stream)
+            # the one device->host read of a forward, in two steps: the copy into pinned memory is issued here, finish() waits for it
+            pin = self.pin = _pin_take(int(lib.texgs_num_rendered_words(N)))
+            _lib.call(lib.texgs_num_rendered_begin, refs[2], N, pin.data_ptr(), pin.numel(), 0, stream)
+            self.d_ev = torch.cuda.Event()
+            self.d_ev.record(self.cur_stream)
+            if self.entry is None:      # K2 behind the event: the host waits for K1 + the copy only, the device goes on sorting
+                _lib.call(lib.texgs_depth_sort_scan, refs[2], N, stream)
+        return self
+
+    def _plan(self, batched=False):
+        """Validation and the layout of the arena sized by N and the image (not allocated yet).  `batched`: one of the views of a batched
+        front end (_begin_views) -- it builds its own lists whatever the shared-geometry cache holds (the views are different cameras)."""
         lib, st = _lib.load(), self.st
         a = self.args = _check_inputs(st, *self.raw)
         for_backward, count_bins, lazy = self.flags
@@ -401,8 +448,9 @@ class _Forward:
         self.want_counts = bool(count_bins and for_backward and a.texture is not None and USE_TEX_BINS)
         H, W = int(st.image_height), int(st.image_width)
         self.tiles = ((W + _lib.TILE - 1) // _lib.TILE) * ((H + _lib.TILE - 1) // _lib.TILE)
-        cur_stream = torch.cuda.current_stream(device)
+        cur_stream = self.cur_stream = torch.cuda.current_stream(device)
         stream = self.stream = cur_stream.cuda_stream
+        self.binned = None          # (D, fingerprint, event) once a batched front end has built this view's lists
         self.keep = list(a[:10])
         with torch.cuda.device(device):
             self.frame = _make_frame(st, N, a.K, a.R, device, self.keep)
@@ -413,7 +461,7 @@ class _Forward:
                           a.cov3D_precomp is not None)
             self.cam_key = tuple((t.data_ptr(), t._version) for t in (st.viewmatrix, st.projmatrix, st.campos))
             gkey = self.gkey = (device.index, int(stream))
-            entry = _GEOM.get(gkey) if GEOM_CACHE else None
+            entry = _GEOM.get(gkey) if (GEOM_CACHE and not batched) else None
             if entry is not None and not (entry.ints == self.gints and entry.cam_key == self.cam_key):
                 del _GEOM[gkey]         # another view / size: the old lists cannot be shared any more -- let go of their arenas before this
                 entry = None            # forward allocates its own (they stay alive only while a state that shares them does)
@@ -434,30 +482,28 @@ class _Forward:
             fix.add("n_contrib", (H, W), i32)
             if entry is None:
                 self._add_lists(fix)
-            fix.commit()
-            radii = torch.empty(N, dtype=i32, device=device)          # K1 writes every entry (0 for culled)
-            self.geom = _lib.Geom(fix.ptr("rec"), fix.ptr("rec_shade"), fix.ptr("depth"), _ptr(radii), fix.ptr("rect"),
-                                  fix.ptr("tiles_touched"), fix.ptr("offsets"), fix.ptr("scan_temp"), scan_bytes)
-            # everything is allocated BEFORE the one device->host sync, the D-sized buffers from a capacity hint
-            # (largest D seen on this device x 1.25): K1 -> sync (K2 runs meanwhile) -> K3..K6 with little host work between
-            self.outs = (torch.empty(3, H, W, dtype=f32, device=device), torch.empty(1, H, W, dtype=f32, device=device),
-                         torch.empty(3, H, W, dtype=f32, device=device), torch.empty(1, H, W, dtype=f32, device=device), radii)
-            self.img = _lib.Image(*map(_ptr, self.outs[:4]), fix.ptr("final_T"), fix.ptr("n_contrib"), None, None, None, None, None)
-            self.hint_key = (device.index, N, H, W)
-            self.cap = _CAPACITY_HINT.get(self.hint_key, max(4 * N, 1024))
-            self.binning = self.bin_ar = None
-            if entry is None:
-                self._alloc_bin(self.cap, fix)
-            refs = self.refs = [C.byref(x) for x in (self.frame, self.inputs, self.geom)]
-            _lib.call(lib.texgs_preprocess_forward, *refs, stream)
-            # the one device->host read of a forward, in two steps: the copy into pinned memory is issued here, finish() waits for it
-            pin = self.pin = _pin_take(int(lib.texgs_num_rendered_words(N)))
-            _lib.call(lib.texgs_num_rendered_begin, refs[2], N, pin.data_ptr(), pin.numel(), 0, stream)
-            self.d_ev = torch.cuda.Event()
-            self.d_ev.record(cur_stream)
-            if entry is None:           # K2 behind the event: the host waits for K1 + the copy only, the device goes on sorting
-                _lib.call(lib.texgs_depth_sort_scan, refs[2], N, stream)
-        return self
+            self.scan_bytes = scan_bytes
+
+    def _bind(self, batched=False):
+        """With the arena in place: the outputs, the structs of the C ABI and -- unless `batched`, where the instance counts are known
+        before anything of that size is needed -- the arena sized by the instance capacity."""
+        a, st, fix, entry, scan_bytes = self.args, self.st, self.fix, self.entry, self.scan_bytes
+        device, N, H, W = a.means3D.device, a.N, int(st.image_height), int(st.image_width)
+        i32, f32 = torch.int32, torch.float32
+        radii = torch.empty(N, dtype=i32, device=device)          # K1 writes every entry (0 for culled)
+        self.geom = _lib.Geom(fix.ptr("rec"), fix.ptr("rec_shade"), fix.ptr("depth"), _ptr(radii), fix.ptr("rect"),
+                              fix.ptr("tiles_touched"), fix.ptr("offsets"), fix.ptr("scan_temp"), scan_bytes)
+        # everything is allocated BEFORE the one device->host sync, the D-sized buffers from a capacity hint
+        # (largest D seen on this device x 1.25): K1 -> sync (K2 runs meanwhile) -> K3..K6 with little host work between
+        self.outs = (torch.empty(3, H, W, dtype=f32, device=device), torch.empty(1, H, W, dtype=f32, device=device),
+                     torch.empty(3, H, W, dtype=f32, device=device), torch.empty(1, H, W, dtype=f32, device=device), radii)
+        self.img = _lib.Image(*map(_ptr, self.outs[:4]), fix.ptr("final_T"), fix.ptr("n_contrib"), None, None, None, None, None)
+        self.hint_key = (device.index, N, H, W)
+        self.cap = _CAPACITY_HINT.get(self.hint_key, max(4 * N, 1024))
+        self.binning = self.bin_ar = None
+        if entry is None and not batched:
+            self._alloc_bin(self.cap, fix)
+        self.refs = [C.byref(x) for x in (self.frame, self.inputs, self.geom)]
 
     def _add_lists(self, ar):           # per-tile pieces of the lists (a candidate adds them only if it has to build lists after all)
         ar.add("ranges", (self.tiles, 2), torch.int32)              # zero-filled by K3
@@ -465,8 +511,9 @@ class _Forward:
         if self.handoff:
             _add_handoff(ar, None, self.tiles, self.args.R, self.want_counts)
 
-    def _alloc_bin(self, cap, lists_ar):
-        """The arena sized by the instance capacity; `lists_ar`: where the per-tile pieces are (None: nowhere yet -- they go in here too)."""
+    def _alloc_bin(self, cap, lists_ar, commit=True):
+        """The arena sized by the instance capacity; `lists_ar`: where the per-tile pieces are (None: nowhere yet -- they go in here too).
+        commit=False: only laid out -- the caller places it in a step buffer and calls _bind_bin."""
         c1, tiles = max(cap, 1), self.tiles
         sort_bytes = _lib.load().texgs_sort_temp_bytes(cap, tiles)
         ar = self.bin_ar = _Arena(self.fix.device)
@@ -478,7 +525,14 @@ class _Forward:
             self._add_lists(ar)
         if self.handoff:
             _add_handoff(ar, cap, None, self.args.R, self.want_counts)
-        ar.commit()
+        self.sort_bytes = sort_bytes
+        if commit:
+            ar.commit()
+            self._bind_bin(lists_ar)
+        return ar
+
+    def _bind_bin(self, lists_ar):
+        ar, sort_bytes = self.bin_ar, self.sort_bytes
         la = lists_ar if lists_ar is not None else ar
         self.binning = _lib.Binning(0, ar.ptr("keys_unsorted"), ar.ptr("keys_sorted"), ar.ptr("point_list"), la.ptr("ranges"),
                                     la.ptr("tile_order"), ar.ptr("sort_temp"), sort_bytes)
@@ -489,6 +543,18 @@ class _Forward:
         lib, a, img, entry, refs = _lib.load(), self.args, self.img, self.entry, self.refs
         for_backward, _, lazy = self.flags
         stream, cap, pin = self.stream, self.cap, self.pin
+        if self.binned is not None:
+            # a view of a batched front end (_begin_views): K1..K5 ran with the other views' and D was read back there; what is left
+            # is K6, on the stream this forward is called on -- ordered behind the batch's launches by their event, whatever that stream is
+            D, fp, ready = self.binned
+            shared, binning = False, self.binning
+            with torch.cuda.device(a.means3D.device):
+                cur = torch.cuda.current_stream(a.means3D.device)
+                if cur.cuda_stream != stream:
+                    cur.wait_event(ready)
+                from .multiview import views_entries
+                _lib.call(views_entries().render_forward_binned, *refs, C.byref(binning), C.byref(img), cur.cuda_stream)
+            return self._finished(binning, D, cap, shared, fp)
         with torch.cuda.device(a.means3D.device):
             self.d_ev.synchronize()
             d_host, fp_host = C.c_uint32(0), C.c_uint64(0)
@@ -523,6 +589,11 @@ class _Forward:
                         self.gints, self.cam_key, fp, D, cap, tuple(getattr(binning, n) for n, _ in _lib.Binning._fields_[1:]),
                         (self.fix, self.bin_ar), (img.survivors, img.surv_qmask, img.surv_count) if self.handoff else None,
                         (img.tex_bin_count, img.tex_bin_resv) if (self.handoff and img.tex_bin_count) else None)
+        return self._finished(binning, D, cap, shared, fp)
+
+    def _finished(self, binning, D, cap, shared, fp):
+        a, img, entry = self.args, self.img, self.entry
+        for_backward, _, lazy = self.flags
         arenas = (self.fix,) + ((self.bin_ar,) if self.bin_ar is not None else ()) + (tuple(entry.arenas) if shared else ())
         # (NOT the output tensors: autograd hangs its node on them, the node holds this state -- a cycle that kept every dropped
         #  graph's buffers alive until the garbage collector ran)
@@ -530,13 +601,199 @@ class _Forward:
         for n in _HANDOFF:          # no hand-off in this state (forward-only call, lazy mode, or a shared entry without one)
             if getattr(img, n) is None:
                 tensors[n] = None
-        return self.outs, _State(self.frame, self.inputs, self.geom, binning, img, tensors, a, D, cap, self.tiles, self.want_counts,
-                                 bool(lazy and for_backward), shared)
+        state = _State(self.frame, self.inputs, self.geom, binning, img, tensors, a, D, cap, self.tiles, self.want_counts,
+                       bool(lazy and for_backward), shared)
+        state.fingerprint = fp
+        return self.outs, state
 
     def abandon(self):
         """A begun forward that will never be finished: its pinned block may go back to the pool only when the copy into it has landed."""
+        if self.binned is not None:         # a view of a batched front end: its counts were read back there, nothing is in flight to the host
+            return
         self.d_ev.synchronize()
         _pin_give(self.pin)
+
+
+# ---- the batched front end: K1..K5 of the views of one multi-view step in one set of launches ------------------------------------
+# Inside `with batched_prefetch():` prefetch_forward / GaussianRasterizer.prefetch only REGISTER their forward, with the stream they
+# were called on.  On exit the requests are grouped: the same input tensors (storage, version, shape), image size, sh_degree, debug
+# flag and for_backward / count_bins / lazy flags, on one device -- different cameras.  Every group of two or more runs K1..K5 once,
+# on the stream current at the exit, through the entry points of include/texgs_multiview.h (_begin_views): K1 reads the SH rows once for
+# all views, K2..K5 take the view as a grid dimension, ONE readback brings every view's instance count.  Each view is then left in
+# _PREFETCH under the stream it was registered on, exactly as a prefetched forward that has begun, except that its forward has only K6
+# left to run.  A request that fits no group (alone in its group, N == 0) takes today's path: begun at the exit, or -- begin_rest=False,
+# which ViewPipeline.run uses to keep its one-view-per-stream-ahead rhythm for those -- left to the caller (request.batched is False).
+# Groups of more than BATCH_MAX_VIEWS are cut into runs of that many.  The shared-geometry cache is bypassed for batched views.
+_BATCH_SCOPE = None
+
+
+class _Request:
+    __slots__ = ("fwd", "stream", "batched")
+
+    def __init__(self, fwd, stream):
+        self.fwd, self.stream, self.batched = fwd, stream, False
+
+
+def group_requests(keys, max_views, min_views=2):
+    """Indices of `keys` -> (groups, rest): the runs of at most `max_views` requests with equal keys, in first-seen order, that hold at
+    least `min_views` requests; `rest`: the indices left alone.  Pure (the grouping rule of batched_prefetch, testable without a device)."""
+    by_key = {}
+    for i, k in enumerate(keys):
+        by_key.setdefault(k, []).append(i)
+    groups, rest = [], []
+    for idx in by_key.values():
+        for lo in range(0, len(idx), max_views):
+            run = idx[lo:lo + max_views]
+            (groups if len(run) >= min_views else rest).append(run)
+    return groups, sorted(i for run in rest for i in run)
+
+
+def _batch_key(fwd):
+    t = lambda x: None if x is None else (x.data_ptr(), x._version, tuple(x.shape), x.dtype, x.device)
+    st = fwd.st
+    return (int(st.image_height), int(st.image_width), int(st.sh_degree), bool(st.debug)) + tuple(t(x) for x in fwd.raw) + fwd.flags
+
+
+class batched_prefetch:
+    """Context manager: the forwards prefetched inside begin together at the exit (see above).  `requests`: what was registered, in
+    order; nested scopes join the outermost one.  `min_views` (default 2; 1: a view alone goes through the batched entry points too, with
+    one view in their tables -- nothing is gained, the kernels are the same; tests).
+
+    The views of a scope are meant to be forwarded before the next scope closes: batched forwards of EARLIER scopes that are still parked
+    then (their forward never came, or came with other tensors, versions or another stream) are dropped at that point -- each keeps its
+    group's step buffers alive --, and such a forward simply runs per view if it is called after all."""
+
+    def __init__(self, begin_rest=True, min_views=2):
+        self.begin_rest, self.min_views, self.requests, self.outer = begin_rest, max(1, int(min_views)), [], None
+
+    def __enter__(self):
+        global _BATCH_SCOPE
+        self.outer = _BATCH_SCOPE
+        if self.outer is None:
+            _BATCH_SCOPE = self
+        else:
+            self.requests = self.outer.requests
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        global _BATCH_SCOPE
+        if self.outer is not None:
+            return False
+        _BATCH_SCOPE = None
+        if exc_type is not None:
+            return False            # nothing was launched for the registered forwards: they run when they are called
+        from .multiview import BATCH_MAX_VIEWS
+        reqs = self.requests
+        groups, rest = group_requests([_batch_key(r.fwd) if r.fwd.raw[0].shape[0] > 0 else ("empty", i) for i, r in enumerate(reqs)],
+                                      BATCH_MAX_VIEWS, self.min_views)
+        if groups:
+            _drop_parked_batched()
+        for run in groups:
+            _begin_views([reqs[i] for i in run])
+        if self.begin_rest:
+            for i in rest:
+                with torch.cuda.stream(reqs[i].stream):
+                    _register_begun(reqs[i].fwd.begin(), limit=4)
+        return False
+
+
+def _drop_parked_batched():
+    """Batched forwards that no view picked up (batched_prefetch: dropped when the next scope batches): out of _PREFETCH, and with them
+    the last references to their step buffers."""
+    for key in list(_PREFETCH):
+        lst = _PREFETCH[key] = [(k, f) for k, f in _PREFETCH[key] if f.binned is None]
+        if not lst:
+            del _PREFETCH[key]
+
+
+def _register_begun(fwd, limit=None):
+    device = fwd.args.means3D.device
+    lst = _PREFETCH.setdefault((device.index, int(torch.cuda.current_stream(device).cuda_stream)), [])
+    lst.append((fwd.key(), fwd))
+    if limit is not None:
+        for _, old in lst[:-limit]:
+            old.abandon()
+        del lst[:-limit]
+
+
+def _begin_views(reqs):
+    """K1..K5 of the forwards in `reqs` (one group of batched_prefetch, 2..BATCH_MAX_VIEWS views) on the current stream; every forward
+    ends up in _PREFETCH under its own stream with its lists built."""
+    from .multiview import views_entries
+    lib, ent = _lib.load(), views_entries()
+    fwds = [r.fwd for r in reqs]
+    device = fwds[0].raw[0].device
+    V = len(fwds)
+    with torch.cuda.device(device):
+        for f in fwds:
+            f._plan(batched=True)
+        a, N = fwds[0].args, fwds[0].args.N
+        cur = torch.cuda.current_stream(device)
+        others = {int(r.stream.cuda_stream): r.stream for r in reqs if r.stream.cuda_stream != cur.cuda_stream}
+
+        def place(arenas, extra=0):
+            """One step buffer for these arenas (+ `extra` bytes behind them) -> (buffer, offset of the extra bytes)"""
+            offs, total = [], 0
+            for ar in arenas:
+                offs.append(total)
+                total = (total + ar.size + 255) & ~255
+            sb = _StepBuffer(total + extra, device)
+            for s in others.values():           # used on the views' streams too: the allocator must not hand it out again before they are done
+                sb.buf.record_stream(s)
+            for ar, off in zip(arenas, offs):
+                ar.place(sb, off)
+            return sb, total
+
+        words = int(lib.texgs_num_rendered_words(N))
+        sb, sums_off = place([f.fix for f in fwds], extra=4 * V * words)
+        sums = sb.buf[sums_off:sums_off + 4 * V * words].view(torch.int32)
+        for f, r in zip(fwds, reqs):
+            f._bind(batched=True)
+            f.stream, f.cur_stream = int(cur.cuda_stream), cur          # (where this forward's K1..K5 run)
+            if r.stream.cuda_stream != cur.cuda_stream:
+                # made on this stream, used by K6..K8 on the view's: the outputs, and whatever _check_inputs / _make_frame had to copy
+                # (an input or a camera tensor that was not contiguous f32) -- `keep` holds those beside the caller's own tensors
+                for t in list(f.outs) + [t for t in f.keep if t is not None and t.is_cuda]:
+                    t.record_stream(r.stream)
+        frames = (_lib.Frame * V)(*[f.frame for f in fwds])
+        geoms = (_lib.Geom * V)(*[f.geom for f in fwds])
+        stream = cur.cuda_stream
+        _lib.call(ent.preprocess_forward_views, frames, C.byref(fwds[0].inputs), geoms, V, sums.data_ptr(), stream)
+        # ONE device->host read for all views; K2 of all views runs behind it while the host waits
+        pin = _pin_take(V * words)
+        pin.copy_(sums, non_blocking=True)
+        d_ev = torch.cuda.Event()
+        d_ev.record(cur)
+        _lib.call(ent.depth_sort_scan_views, geoms, N, V, stream)
+        d_ev.synchronize()
+        counts = []
+        d_host, fp_host = C.c_uint32(0), C.c_uint64(0)
+        for v in range(V):
+            _lib.call(lib.texgs_num_rendered_reduce, pin.data_ptr() + 4 * v * words, N, C.byref(d_host), C.byref(fp_host))
+            counts.append((int(d_host.value), int(fp_host.value)))
+        _pin_give(pin)
+        # the arenas sized by the instance counts: exact per view (+ rounding), one allocation whose size follows the largest sum seen
+        for f, (D, _) in zip(fwds, counts):
+            f.cap = (max(D, 1) + 1023) & ~1023
+            f._alloc_bin(f.cap, f.fix, commit=False)
+        need = sum((f.bin_ar.size + 255) & ~255 for f in fwds)
+        hint_key = ("views", device.index, N, fwds[0].gints[1], fwds[0].gints[2], V)
+        hint = _CAPACITY_HINT.get(hint_key, 0)
+        if need > hint:
+            hint = _CAPACITY_HINT[hint_key] = need + need // 8
+        place([f.bin_ar for f in fwds], extra=hint - need)
+        for f, (D, _) in zip(fwds, counts):
+            f._bind_bin(f.fix)
+            f.binning.num_rendered = D
+        bins = (_lib.Binning * V)(*[f.binning for f in fwds])
+        imgs = (_lib.Image * V)(*[f.img for f in fwds])
+        _lib.call(ent.bin_sort_views, frames, geoms, bins, imgs, V, stream)
+        ready = torch.cuda.Event()
+        ready.record(cur)
+    for f, r, (D, fp) in zip(fwds, reqs, counts):
+        f.binned, f.pin, r.batched = (D, fp, ready), None, True
+        with torch.cuda.stream(r.stream):
+            _register_begun(f)
 
 
 def _gpu_only(device):
@@ -551,16 +808,16 @@ def prefetch_forward(st, means3D, shs, opacities, scales, rotations, uvs, gradie
     """Begin a forward now -- K1, the asynchronous D readback, K2 -- on the current stream; a later forward_raw / GaussianRasterizer
     call on this stream with the same arguments (same tensor storages and versions, same settings, same flags) finishes it without
     waiting for the device.  At most four forwards are kept pending per stream (older ones are dropped: their K1 was wasted, and the
-    host waits for it once).  Returns nothing."""
+    host waits for it once).  Inside `with batched_prefetch():` the forward is only registered and begins when the scope closes, together
+    with the other views registered there (K1..K5 once for all of them).  Returns nothing."""
     device = means3D.device
     _gpu_only(device)
     fwd = _Forward(st, (means3D, shs, opacities, scales, rotations, uvs, gradient_uvs, texture, color_offset, cov3D_precomp),
-                   for_backward, count_bins, lazy).begin()
-    lst = _PREFETCH.setdefault((device.index, int(torch.cuda.current_stream(device).cuda_stream)), [])
-    lst.append((fwd.key(), fwd))
-    for _, old in lst[:-4]:
-        old.abandon()
-    del lst[:-4]
+                   for_backward, count_bins, lazy)
+    if _BATCH_SCOPE is not None:        # inside batched_prefetch: begun at its exit, together with the other views of the step
+        _BATCH_SCOPE.requests.append(_Request(fwd, torch.cuda.current_stream(device)))
+        return
+    _register_begun(fwd.begin(), limit=4)
 
 
 def forward_raw(st, means3D, shs, opacities, scales, rotations, uvs, gradient_uvs, texture, color_offset=None,
