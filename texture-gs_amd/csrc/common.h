@@ -11,6 +11,7 @@
 #include "texgs_surface.h"
 #include "texgs_lpips.h"
 #include "texgs_lpips_grad.h"
+#include "texgs_params.h"
 
 // ---- operator constants (restated in oracle/texgs_torch.py) ----
 #define TG_NEAR_Z        0.2f
@@ -164,3 +165,8 @@ size_t lpips_head_temp_bytes(int P, int h, int w);
 hipError_t launch_lpips_head(const TexGSLpipsHead* d, hipStream_t s);
 hipError_t launch_lpips_head_backward(const TexGSLpipsHeadBackward* d, hipStream_t s);      // lpips_grad.hip, validated by abi.hip
 hipError_t launch_lpips_gate(float* G, const float* y, long long n, hipStream_t s);
+size_t params_temp_bytes(int32_t n);                // params.hip; the arguments of these are validated by the caller (abi.hip), n >= 1
+hipError_t launch_params_activate(const TexGSParamsActivate* a, void* temp, hipStream_t s);
+hipError_t launch_params_activate_backward(const TexGSParamsActivateGrad* g, hipStream_t s);
+hipError_t launch_params_covariance(const TexGSParamsCovariance* c, hipStream_t s);
+hipError_t launch_params_covariance_backward(const TexGSParamsCovarianceGrad* c, hipStream_t s);
