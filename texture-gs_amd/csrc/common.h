@@ -12,6 +12,7 @@
 #include "texgs_lpips.h"
 #include "texgs_lpips_grad.h"
 #include "texgs_params.h"
+#include "texgs_retexture.h"
 
 // ---- operator constants (restated in oracle/texgs_torch.py) ----
 #define TG_NEAR_Z        0.2f
@@ -170,3 +171,5 @@ hipError_t launch_params_activate(const TexGSParamsActivate* a, void* temp, hipS
 hipError_t launch_params_activate_backward(const TexGSParamsActivateGrad* g, hipStream_t s);
 hipError_t launch_params_covariance(const TexGSParamsCovariance* c, hipStream_t s);
 hipError_t launch_params_covariance_backward(const TexGSParamsCovarianceGrad* c, hipStream_t s);
+hipError_t launch_retexture_cross(const TexGSRetexCross* c, hipStream_t s);        // retexture.hip, validated by abi.hip
+hipError_t launch_retexture_latlong(const TexGSRetexLatLong* l, hipStream_t s);
