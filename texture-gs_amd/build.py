@@ -8,7 +8,8 @@ ingest.hip (its fp64 tap tables are compared with Pillow's, its bytes and floats
 dot products are compared with numpy's bit for bit) and lpips.hip (its head's (a - b)^2 must equal (b - a)^2 bit for bit) and
 lpips_grad.hip (the gradient of the partner must equal the gradient of the first image of the swapped pair bit for bit) and
 params.hip (its row arithmetic is compared with numpy's bit for bit, exp and log included) and
-retexture.hip (its fp64 taps and blend and its fp32 mode arithmetic are compared with numpy's bit for bit);
+retexture.hip (its fp64 taps and blend and its fp32 mode arithmetic are compared with numpy's bit for bit) and
+shcolor.hip (its SH evaluation and view direction are compared with numpy's bit for bit);
 the render kernels allow contraction
 and use hardware fp32 atomics (-munsafe-fp-atomics).
 """
@@ -49,6 +50,7 @@ UNITS = {
     "lpips_grad.hip": ["-ffp-contract=off"],  # d img1 of (a, b) must equal d img0 of (b, a) bit for bit: one rounding per operation
     "params.hip": ["-ffp-contract=off"],      # the row arithmetic is a bit-exact contract and a row's bits must not depend on n or its position
     "retexture.hip": ["-ffp-contract=off"],   # the fp64 resize and the fp32 mode arithmetic are a bit-exact contract: one rounding per operation
+    "shcolor.hip": ["-ffp-contract=off"],     # the SH evaluation in the reference's operation order is a bit-exact contract: one rounding per operation
     "abi.hip": [],
 }
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "wave_ops.h"), os.path.join(CSRC, "render_bwd_body.h"),
@@ -58,7 +60,8 @@ HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "wave_ops.h"), os.
            os.path.join(ROOT, "include", "texgs_surface.h"), os.path.join(ROOT, "include", "texgs_lpips.h"),
            os.path.join(ROOT, "include", "texgs_lpips_grad.h"), os.path.join(ROOT, "include", "texgs_params.h"),
            os.path.join(CSRC, "params_math.h"), os.path.join(ROOT, "include", "texgs_retexture.h"),
-           os.path.join(CSRC, "retexture_math.h")]
+           os.path.join(CSRC, "retexture_math.h"), os.path.join(ROOT, "include", "texgs_shcolor.h"),
+           os.path.join(CSRC, "shcolor_math.h")]
 
 
 def build_id():
@@ -69,7 +72,7 @@ def build_id():
     h = hashlib.sha256()
     files = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))) \
         + [os.path.join(ROOT, "include", f) for f in ("texgs.h", "texgs_optim.h", "texgs_multiview.h", "texgs_mlp.h", "texgs_present.h", "texgs_ingest.h",
-                                                         "texgs_surface.h", "texgs_lpips.h", "texgs_lpips_grad.h", "texgs_params.h", "texgs_retexture.h")]
+                                                         "texgs_surface.h", "texgs_lpips.h", "texgs_lpips_grad.h", "texgs_params.h", "texgs_retexture.h", "texgs_shcolor.h")]
     for f in files:
         h.update(os.path.basename(f).encode())
         h.update(open(f, "rb").read())

@@ -13,6 +13,7 @@
 #include "texgs_lpips_grad.h"
 #include "texgs_params.h"
 #include "texgs_retexture.h"
+#include "texgs_shcolor.h"
 
 // ---- operator constants (restated in oracle/texgs_torch.py) ----
 #define TG_NEAR_Z        0.2f
@@ -173,3 +174,5 @@ hipError_t launch_params_covariance(const TexGSParamsCovariance* c, hipStream_t 
 hipError_t launch_params_covariance_backward(const TexGSParamsCovarianceGrad* c, hipStream_t s);
 hipError_t launch_retexture_cross(const TexGSRetexCross* c, hipStream_t s);        // retexture.hip, validated by abi.hip
 hipError_t launch_retexture_latlong(const TexGSRetexLatLong* l, hipStream_t s);
+hipError_t launch_sh_colors(const TexGSShColors* c, const TexGSShColorView* views, int count, hipStream_t s);      // shcolor.hip, validated by abi.hip
+hipError_t launch_sh_colors_backward(const TexGSShColorsGrad* g, const TexGSShColorGradView* views, int count, hipStream_t s);
