@@ -9,6 +9,9 @@ import sys
 
 import pytest
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import abi_check  # noqa: E402
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HDR = os.path.join(ROOT, "include", "texgs.h")
 
@@ -56,98 +59,65 @@ def test_ctypes_structs_match_c_layout(tmp_path):
               "TEXGS_TEXBIN_RECORD_FLOATS": _lib.TEXBIN_RECORD_FLOATS, "TEXGS_RESV_WORDS": _lib.RESV_WORDS,
               "TEXGS_DENSITY_MAX_ROWS": _lib.DENSITY_MAX_ROWS, "TEXGS_METRICS_ROW": _lib.METRICS_ROW,
               "TEXGS_HASHGRID_MAX_LEVELS": _lib.HASHGRID_MAX_LEVELS, "TEXGS_HASHGRID_FEATURES": _lib.HASHGRID_FEATURES}
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "texgs.h"', 'int main(void) {']
-    for cname, cls in structs.items():
-        lines.append(f'printf("{cname} %zu\\n", sizeof({cname}));')
-        for fname, _ in cls._fields_:
-            lines.append(f'printf("{cname}.{fname} %zu\\n", offsetof({cname}, {fname}));')
-    for cname in consts:
-        lines.append(f'printf("{cname} %d\\n", (int)({cname}));')
-    lines.append('return 0; }')
-    src = tmp_path / "layout.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "layout"
-    subprocess.check_call(["gcc", "-std=c99", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    out = subprocess.check_output([str(exe)]).decode().split("\n")
-    got = {l.split()[0]: l.split()[1:] for l in out if l.strip()}
-    for cname, cls in structs.items():
-        assert int(got[cname][0]) == ctypes.sizeof(cls), cname
-        for fname, _ in cls._fields_:
-            assert int(got[f"{cname}.{fname}"][0]) == getattr(cls, fname).offset, (cname, fname)
-    for cname, value in consts.items():
-        assert int(got[cname][0]) == value, cname
+    assert abi_check.layout_mismatches("texgs.h", structs, consts, tmp_path) == []
 
 
-def header_prototypes():
-    """{name: (return type, [argument types])} of every function that include/texgs.h declares, as C type strings without the
-    argument names and without `const` (`const TexGSFrame* frame` -> `TexGSFrame*`)."""
-    src = open(HDR).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    src = re.sub(r"//[^\n]*", "", src)
-    ctype = lambda decl: re.sub(r"\s+", "", re.sub(r"\bconst\b", "", decl))
-    protos = {}
-    for ret, name, args in re.findall(r"^\s*((?:const\s+)?\w+\s*\*?)\s*(texgs_\w+)\s*\(([^)]*)\)\s*;", src, flags=re.M):
-        args = [a.strip() for a in args.split(",")]
-        args = [] if args == ["void"] else [ctype(re.sub(r"\w+$", "", a)) for a in args]       # drop the argument's name
-        protos[name] = (ctype(ret), args)
-    return protos
-
-
-C_SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "uint32_t": ctypes.c_uint32, "size_t": ctypes.c_size_t,
-             "float": ctypes.c_float}
-
-
-def same_scalar(a, b):
-    """Two ctypes scalar types of the same width and kind (signed / unsigned integer, float)"""
-    kind = lambda t: "int" if t._type_ in "bhilq" else "uint" if t._type_ in "BHILQ" else t._type_
-    simple = lambda t: isinstance(t, type) and issubclass(t, ctypes._SimpleCData) and t._type_ in "bhilqBHILQfd"
-    return simple(a) and simple(b) and ctypes.sizeof(a) == ctypes.sizeof(b) and kind(a) == kind(b)
-
-
-def signature_mismatches(signatures):
-    """Every disagreement between a {name: (restype, argtypes)} table and the header's prototypes, as strings"""
-    protos, structs, bad = header_prototypes(), mirrors(), []
-    if sorted(signatures) != sorted(protos):
-        bad.append(f"names differ: {sorted(set(signatures) ^ set(protos))}")
-    for name, (restype, argtypes) in signatures.items():
-        if name not in protos:
-            continue
-        ret, args = protos[name]
-        if not (restype is ctypes.c_char_p if ret == "char*" else same_scalar(restype, C_SCALARS[ret])):
-            bad.append(f"{name}: returns {ret}, the table says {restype}")
-        if len(argtypes) != len(args):
-            bad.append(f"{name}: {len(args)} arguments, the table has {len(argtypes)}")
-            continue
-        for k, (c, t) in enumerate(zip(args, argtypes)):
-            is_pointer = t is ctypes.c_void_p or (isinstance(t, type) and issubclass(t, ctypes._Pointer))
-            if c in C_SCALARS:
-                ok = same_scalar(t, C_SCALARS[c])
-            elif c.endswith("*") and c[:-1] in structs:
-                ok = t is ctypes.c_void_p or t is ctypes.POINTER(structs[c[:-1]])
-            else:
-                ok = c.endswith("*") and not c.startswith("TexGS") and is_pointer
-            if not ok:
-                bad.append(f"{name}: argument {k} is {c}, the table says {t}")
-    return bad
+def broken_tables_are_caught(header, signatures, mirrors, dropped, widened, swapped):
+    """The check sees what it is for.  `dropped`: an entry point that loses its last argument; `widened`: (entry point, argument) of an
+    int32_t stated as size_t; `swapped`: (entry point, argument, another struct's mirror) of a struct pointer."""
+    def mismatches(name, k=None, t=None):
+        restype, argtypes = signatures[name]
+        argtypes = argtypes[:-1] if k is None else argtypes[:k] + [t] + argtypes[k + 1:]
+        return abi_check.signature_mismatches(header, dict(signatures, **{name: (restype, argtypes)}), mirrors)
+    protos = abi_check.prototypes(header)
+    assert any(f"{dropped}: {len(protos[dropped][1])} arguments" in m for m in mismatches(dropped))
+    name, k = widened
+    assert protos[name][1][k] == "int32_t" and any(f"{name}: argument {k} is int32_t" in m for m in mismatches(name, k, ctypes.c_size_t))
+    name, k, other = swapped
+    assert any(f"{name}: argument {k} is {protos[name][1][k]}" in m for m in mismatches(name, k, ctypes.POINTER(other)))
 
 
 def test_signature_table_matches_the_header():
     """texgs/_lib.py states each entry point's ctypes signature once (SIGNATURES); every one is compared with its prototype in
     include/texgs.h: the return type, the argument count, and per argument a scalar of the same width and kind, the mirror of the
-    TexGS* struct pointed to (or void*), or a pointer for any other pointer.  ctypes converts silently, so a wrong width or a missing
-    argument would otherwise corrupt a call instead of failing it."""
+    TexGS* struct pointed to, or a pointer for any other pointer (tests/abi_check.py, as every stage's test does for its own header).
+    ctypes converts silently, so a wrong width or a missing argument would otherwise corrupt a call instead of failing it."""
     from texgs import _lib
-    assert len(header_prototypes()) == 49
-    assert signature_mismatches(_lib.SIGNATURES) == []
-    # the check sees what it is for: one argument dropped, one int32_t widened to size_t, one struct mirror swapped
-    broken = dict(_lib.SIGNATURES)
-    ret, args = broken["texgs_cube_latlong"]
-    broken["texgs_cube_latlong"] = (ret, args[:-1])
-    assert any("texgs_cube_latlong: 8 arguments" in m for m in signature_mismatches(broken))
-    broken = dict(_lib.SIGNATURES, texgs_scan_temp_bytes=(ctypes.c_size_t, [ctypes.c_size_t]))
-    assert any("texgs_scan_temp_bytes: argument 0 is int32_t" in m for m in signature_mismatches(broken))
-    broken = dict(_lib.SIGNATURES, texgs_density_move=(ctypes.c_int, [ctypes.POINTER(_lib.DensityPlanStruct), ctypes.c_void_p]))
-    assert any("texgs_density_move: argument 0 is TexGSDensityMove*" in m for m in signature_mismatches(broken))
+    assert len(abi_check.prototypes(HDR)) == 49
+    assert abi_check.signature_mismatches(HDR, _lib.SIGNATURES, mirrors()) == []
+    # one argument dropped, one int32_t widened to size_t, one struct mirror swapped
+    broken_tables_are_caught(HDR, _lib.SIGNATURES, mirrors(), "texgs_cube_latlong", ("texgs_scan_temp_bytes", 0),
+                             ("texgs_density_move", 0, _lib.DensityPlanStruct))
+
+
+def test_a_stage_headers_broken_table_is_caught_too():
+    """The same three breakages against a stage's header and the table in the stage's module (texgs_params.h, texgs.params)"""
+    from texgs import params
+    header = os.path.join(ROOT, "include", "texgs_params.h")
+    assert abi_check.signature_mismatches(header, params.SIGNATURES, params.MIRRORS) == []
+    broken_tables_are_caught(header, params.SIGNATURES, params.MIRRORS, "texgs_params_activate", ("texgs_params_temp_bytes", 0),
+                             ("texgs_params_covariance", 0, params.ParamsCovarianceGradStruct))
+    renamed = {("texgs_params_size" if n == "texgs_params_temp_bytes" else n): v for n, v in params.SIGNATURES.items()}
+    assert any("names differ" in m and "texgs_params_size" in m for m in abi_check.signature_mismatches(header, renamed, params.MIRRORS))
+    void = dict(params.SIGNATURES, texgs_params_covariance=(ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]))
+    assert any("texgs_params_covariance: argument 0" in m for m in abi_check.signature_mismatches(header, void, params.MIRRORS))
+
+
+def test_bind_applies_a_table_once_and_names_every_missing_export(lib_built):
+    """_lib.bind(table): the loaded library with the table applied; a table that names symbols the library lacks raises the rebuild
+    advice with every one of them, and is not remembered; the same table a second time is the same library with argtypes as stated."""
+    from texgs import _lib
+    lib = _lib.load()
+    absent = {"texgs_no_such_entry": (ctypes.c_int, []), "texgs_tex_bin_count": _lib.SIGNATURES["texgs_tex_bin_count"],
+              "texgs_nor_this_one": (ctypes.c_int, [ctypes.c_void_p])}
+    for _ in range(2):
+        with pytest.raises(RuntimeError, match=r"does not export texgs_no_such_entry, texgs_nor_this_one; rebuild it with "
+                                               r"`python texture-gs_amd/build.py`"):
+            _lib.bind(absent)
+    table = {"texgs_scan_temp_bytes": (ctypes.c_size_t, [ctypes.c_int32]), "texgs_abi_version": (ctypes.c_int, [])}
+    assert _lib.bind(table) is lib and _lib.bind(table) is lib and _lib.bind(_lib.SIGNATURES) is lib
+    assert lib.texgs_scan_temp_bytes.argtypes == [ctypes.c_int32] and lib.texgs_scan_temp_bytes.restype is ctypes.c_size_t
+    assert lib.texgs_abi_version() == _lib.ABI_VERSION
 
 
 def test_call_raises_with_the_entry_points_name(lib_built):

@@ -4,8 +4,12 @@ ViewPipeline.run's use of the batch scope (with recorded streams; no device)."""
 import ctypes
 import os
 import re
+import sys
 
 import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import abi_check  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INC = os.path.join(ROOT, "include")
@@ -16,23 +20,16 @@ def test_signatures_match_the_header(lib_built):
     library exports every one; the ABI number is unchanged (the addition is additive: no struct or earlier entry point moved)"""
     from texgs import _lib
     from texgs import multiview as MV
-    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(INC, "texgs_multiview.h")).read(), flags=re.S)
-    protos = {n: [a.strip() for a in args.split(",")] for n, args in re.findall(r"\bint\s+(texgs_\w+)\s*\(([^)]*)\)\s*;", hdr)}
+    hdr = os.path.join(INC, "texgs_multiview.h")
     sigs = MV.views_signatures()
-    assert set(protos) == set(sigs) | {"texgs_sh_flush"}
-    mirror = {"TexGSFrame": _lib.Frame, "TexGSInputs": _lib.Inputs, "TexGSGeom": _lib.Geom, "TexGSBinning": _lib.Binning, "TexGSImage": _lib.Image}
+    assert sigs is MV.views_signatures()            # a table built once
+    assert set(abi_check.prototypes(hdr)) == set(sigs) | {"texgs_sh_flush"}
+    mirror = {"TexGSFrame": _lib.Frame, "TexGSInputs": _lib.Inputs, "TexGSGeom": _lib.Geom, "TexGSBinning": _lib.Binning, "TexGSImage": _lib.Image,
+              "TexGSShFlushView": MV.ShFlushView}
+    assert abi_check.signature_mismatches(hdr, {"texgs_sh_flush": MV.SH_FLUSH_SIGNATURE, **sigs}, mirror) == []
     lib = ctypes.CDLL(lib_built)
-    for name, (restype, argtypes) in sigs.items():
-        assert restype is ctypes.c_int and hasattr(lib, name), name
-        assert len(argtypes) == len(protos[name]), name
-        for decl, t in zip(protos[name], argtypes):
-            ctype = re.sub(r"\s+", "", re.sub(r"\bconst\b", "", re.sub(r"\w+$", "", decl)))
-            if ctype == "int32_t":
-                assert t is ctypes.c_int32, (name, decl)
-            elif ctype.rstrip("*") in mirror:
-                assert t is ctypes.POINTER(mirror[ctype.rstrip("*")]), (name, decl)
-            else:
-                assert ctype.endswith("*") and t is ctypes.c_void_p, (name, decl)
+    assert all(restype is ctypes.c_int and hasattr(lib, name) for name, (restype, _) in sigs.items())
+    hdr = open(hdr).read()
     assert int(re.search(r"#define\s+TEXGS_BATCH_MAX_VIEWS\s+(\d+)", hdr).group(1)) == MV.BATCH_MAX_VIEWS == 16
     assert _lib.load().texgs_abi_version() == _lib.ABI_VERSION
 

@@ -14,6 +14,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import abi_check  # noqa: E402
 import density_ref as R  # noqa: E402
 
 GOLD = R.golden()
@@ -232,24 +233,9 @@ def test_header_exports_and_abi_version(lib_built):
 
 
 def test_struct_layouts_match_the_header(tmp_path):
-    """sizeof and every offsetof of the three new structs as a C compiler sees the header against the ctypes declarations (gcc, as
+    """The size and every field offset of the three new structs as a C compiler sees the header against the ctypes declarations (gcc, as
     tests/test_abi.py compiles its probe: a machine without it fails here, it does not skip)"""
-    import ctypes as C
-    import subprocess
     from texgs import _lib
     structs = {"TexGSDensityPlan": _lib.DensityPlanStruct, "TexGSDensityRow": _lib.DensityRowStruct, "TexGSDensityMove": _lib.DensityMoveStruct}
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "texgs.h"', 'int main(void) {']
-    for name, st in structs.items():
-        lines.append('printf("%%zu", sizeof(%s));' % name)
-        lines += ['printf(" %%zu", offsetof(%s, %s));' % (name, f) for f, _ in st._fields_]
-        lines.append('printf("\\n");')
-    lines.append('printf("%zu %d\\n", sizeof(((TexGSDensityMove*)0)->row) / sizeof(TexGSDensityRow), TEXGS_DENSITY_MAX_ROWS);')
-    lines.append("return 0; }")
-    src = tmp_path / "layout.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "layout"
-    subprocess.check_call(["gcc", "-std=c99", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    got = subprocess.check_output([str(exe)]).decode().split("\n")
-    for line, (name, st) in zip(got, structs.items()):
-        assert [int(x) for x in line.split()] == [C.sizeof(st)] + [getattr(st, f).offset for f, _ in st._fields_], name
-    assert [int(x) for x in got[3].split()] == [_lib.DENSITY_MAX_ROWS, _lib.DENSITY_MAX_ROWS]
+    consts = {"sizeof(((TexGSDensityMove*)0)->row) / sizeof(TexGSDensityRow)": _lib.DENSITY_MAX_ROWS, "TEXGS_DENSITY_MAX_ROWS": _lib.DENSITY_MAX_ROWS}
+    assert abi_check.layout_mismatches("texgs.h", structs, consts, tmp_path) == []

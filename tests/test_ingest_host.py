@@ -17,6 +17,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import abi_check  # noqa: E402
 import ingest_ref as R  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -127,25 +128,7 @@ def test_struct_matches_c_layout(tmp_path):
               "TEXGS_INGEST_PRECISION_BITS": ingest.PRECISION_BITS, "TEXGS_INGEST_MAX_KSIZE": ingest.MAX_KSIZE,
               "TEXGS_INGEST_MAX_SIDE": ingest.MAX_SIDE, "TEXGS_INGEST_SIGNED": ingest.SIGNED}
     assert sorted(ingest.MIRRORS) == ["TexGSResize"]
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "texgs_ingest.h"', 'int main(void) {']
-    for cname, cls in ingest.MIRRORS.items():
-        lines.append(f'printf("{cname} %zu\\n", sizeof({cname}));')
-        lines += [f'printf("{cname}.{f} %zu\\n", offsetof({cname}, {f}));' for f, _ in cls._fields_]
-    lines += [f'printf("{k} %d\\n", (int){k});' for k in consts] + ['return 0; }']
-    src = tmp_path / "layout.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "layout"
-    subprocess.check_call(["gcc", "-std=c99", "-I", INC, str(src), "-o", str(exe)])
-    got = dict(l.split() for l in subprocess.check_output([str(exe)]).decode().split("\n") if l.strip())
-    for cname, cls in ingest.MIRRORS.items():
-        assert int(got[cname]) == C.sizeof(cls), cname
-        for f, _ in cls._fields_:
-            assert int(got[f"{cname}.{f}"]) == getattr(cls, f).offset, (cname, f)
-    assert {k: int(got[k]) for k in consts} == consts
-    text = re.sub(r"/\*.*?\*/", "", open(HDR).read(), flags=re.S)
-    for cname, cls in ingest.MIRRORS.items():
-        body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (cname, cname), text, flags=re.S).group(1)
-        assert re.findall(r"(\w+);", body) == [f for f, _ in cls._fields_], cname
+    assert abi_check.layout_mismatches("texgs_ingest.h", ingest.MIRRORS, consts, tmp_path) == []
 
 
 def test_header_is_plain_c99_and_stands_alone(tmp_path):
@@ -158,27 +141,14 @@ def test_header_is_plain_c99_and_stands_alone(tmp_path):
     assert '#include "texgs_ingest.h"' in open(os.path.join(ROOT, "texture-gs_amd", "csrc", "common.h")).read()
 
 
-def _prototypes():
-    src = re.sub(r"/\*.*?\*/", "", open(HDR).read(), flags=re.S)
-    out = {}
-    for ret, name, args in re.findall(r"^\s*(\w+)\s+(texgs_\w+)\s*\(([^)]*)\)\s*;", src, flags=re.M):
-        out[name] = (ret, [re.sub(r"\s+", "", re.sub(r"\bconst\b", "", re.sub(r"\w+$", "", a.strip()))) for a in args.split(",")])
-    return out
-
-
 def test_library_exports_the_entries_and_the_signatures_match_the_prototypes(lib_built):
     from texgs import _lib, ingest, present
-    protos = _prototypes()
+    protos = abi_check.prototypes(HDR)
     assert sorted(protos) == sorted(ingest.SIGNATURES) == sorted(["texgs_resize_ksize", "texgs_resize_taps", "texgs_resize_temp_bytes",
                                                                    "texgs_resize_u8", "texgs_rgba_composite"])
     raw = C.CDLL(lib_built)
-    ctype = {"TexGSResize*": C.POINTER(ingest.ResizeStruct), "void*": C.c_void_p, "int32_t*": C.c_void_p, "uint8_t*": C.c_void_p,
-             "int32_t": C.c_int32, "size_t": C.c_size_t, "double": C.c_double}
-    for name, (ret, args) in protos.items():
-        assert hasattr(raw, name), name
-        restype, argtypes = ingest.SIGNATURES[name]
-        assert restype is {"int": C.c_int, "size_t": C.c_size_t, "int32_t": C.c_int32}[ret], name
-        assert argtypes == [ctype[a] for a in args], (name, args)
+    assert all(hasattr(raw, name) for name in protos)
+    assert abi_check.signature_mismatches(HDR, ingest.SIGNATURES, ingest.MIRRORS) == []
     lib = ingest.entry()
     assert lib is _lib.load() and lib.texgs_resize_u8.argtypes == ingest.SIGNATURES["texgs_resize_u8"][1]
     # its own table: neither the one tests/test_abi.py pins to texgs.h nor the output stage's

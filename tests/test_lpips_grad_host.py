@@ -4,7 +4,6 @@ the refusals that run before any launch or library call, and the autograd wiring
 import ctypes
 import os
 import re
-import subprocess
 import sys
 
 import numpy as np
@@ -13,6 +12,7 @@ import torch
 import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import abi_check  # noqa: E402
 import lpips_grad_ref as GR  # noqa: E402
 import lpips_ref as R  # noqa: E402
 
@@ -154,56 +154,19 @@ def test_a_zero_norm_pixel_gets_a_zero_row_and_nothing_is_nan():
 
 
 # ---- the C side without a GPU ----
-def _prototypes(path=HDR):
-    src = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    out = {}
-    for ret, name, args in re.findall(r"^\s*(\w+\s*\*?)\s*(texgs_\w+)\s*\(([^)]*)\)\s*;", src, flags=re.M):
-        out[name] = (ret.strip(), [a.strip() for a in args.split(",")])
-    return out
-
-
 def test_ctypes_mirror_matches_the_header(tmp_path):
     from texgs import lpips_grad as G
     consts = {"TEXGS_LPIPS_WRT_FIRST": G.WRT_FIRST, "TEXGS_LPIPS_WRT_PARTNER": G.WRT_PARTNER}
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "texgs_lpips_grad.h"', 'int main(void) {']
-    for cname, cls in G.MIRRORS.items():
-        lines.append(f'printf("{cname} %zu\\n", sizeof({cname}));')
-        for fname, _ in cls._fields_:
-            lines.append(f'printf("{cname}.{fname} %zu\\n", offsetof({cname}, {fname}));')
-    for cname in consts:
-        lines.append(f'printf("{cname} %d\\n", (int)({cname}));')
-    lines.append('return 0; }')
-    src = tmp_path / "layout.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "layout"
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-pedantic", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    got = {l.split()[0]: int(l.split()[1]) for l in subprocess.check_output([str(exe)]).decode().split("\n") if l.strip()}
-    for cname, cls in G.MIRRORS.items():
-        assert got[cname] == ctypes.sizeof(cls), cname
-        for fname, _ in cls._fields_:
-            assert got[f"{cname}.{fname}"] == getattr(cls, fname).offset, (cname, fname)
-    for cname, value in consts.items():
-        assert got[cname] == value, cname
+    assert abi_check.layout_mismatches("texgs_lpips_grad.h", G.MIRRORS, consts, tmp_path) == []
     body = re.sub(r"/\*.*?\*/", "", open(HDR).read(), flags=re.S)
     assert re.findall(r"typedef struct (\w+) \{", body) == list(G.MIRRORS)
-    for cname, cls in G.MIRRORS.items():
-        fields = re.search(r"typedef struct %s \{(.*?)\}" % cname, body, flags=re.S).group(1)
-        names = []
-        for decl in (d.strip() for d in fields.split(";")):
-            if decl:
-                parts = decl.split(",")
-                names += [re.findall(r"\w+", parts[0])[-1]] + [p.strip() for p in parts[1:]]
-        assert names == [f for f, _ in cls._fields_], cname
 
 
 def test_every_prototype_has_a_signature_of_the_same_arity(lib_built):
     from texgs import _lib, lpips as L, lpips_grad as G
-    protos = _prototypes()
+    protos = abi_check.prototypes(HDR)
     assert sorted(protos) == sorted(G.SIGNATURES) == ["texgs_lpips_gate", "texgs_lpips_head_backward"]
-    for name, (ret, args) in protos.items():
-        restype, argtypes = G.SIGNATURES[name]
-        assert len(args) == len(argtypes), name
-        assert restype is ctypes.c_int and ret == "int", name
+    assert abi_check.signature_mismatches(HDR, G.SIGNATURES, G.MIRRORS) == []
     lib = ctypes.CDLL(lib_built)
     for name in protos:
         assert hasattr(lib, name), name
@@ -211,7 +174,7 @@ def test_every_prototype_has_a_signature_of_the_same_arity(lib_built):
     assert G.entry().texgs_lpips_gate.argtypes == G.SIGNATURES["texgs_lpips_gate"][1]
     # a table of its own: disjoint from the main one and from the forward's, whose header keeps its five prototypes
     assert not set(G.SIGNATURES) & set(_lib.SIGNATURES) and not set(G.SIGNATURES) & set(L.SIGNATURES) and _lib.ABI_VERSION == 19
-    assert len(_prototypes(os.path.join(ROOT, "include", "texgs_lpips.h"))) == 5 and not hasattr(L, "LpipsHeadBackwardStruct")
+    assert len(abi_check.prototypes(os.path.join(ROOT, "include", "texgs_lpips.h"))) == 5 and not hasattr(L, "LpipsHeadBackwardStruct")
 
 
 def test_entry_points_refuse_before_any_launch(lib_built):
@@ -255,7 +218,7 @@ def test_arguments_are_checked_before_the_library_is_loaded(monkeypatch):
     def no_load():
         raise AssertionError("the library was loaded")
     monkeypatch.setattr(_lib, "load", no_load)
-    monkeypatch.setattr(G, "_lib_ready", None)
+    monkeypatch.setattr(_lib, "_bound", {})             # no table counts as applied: entry() would have to load
     f, lin, gbar = torch.zeros(2, 16, 4, 6), torch.zeros(16), torch.zeros(1)
     with pytest.raises(RuntimeError, match="no CPU fallback"):
         G.head_backward(f, lin, gbar, 1)

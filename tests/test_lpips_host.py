@@ -4,8 +4,6 @@ refusals that run before any launch, the ctypes mirrors of include/texgs_lpips.h
 unchanged result without a net."""
 import ctypes
 import os
-import re
-import subprocess
 import sys
 import warnings
 
@@ -15,6 +13,7 @@ import torch
 import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import abi_check  # noqa: E402
 import lpips_ref as R  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -204,7 +203,7 @@ def test_arguments_are_checked_before_the_library_is_loaded(monkeypatch):
     def no_load():
         raise AssertionError("the library was loaded")
     monkeypatch.setattr(_lib, "load", no_load)
-    monkeypatch.setattr(L, "_lib_ready", None)
+    monkeypatch.setattr(_lib, "_bound", {})             # no table counts as applied: entry() would have to load
     net = L.LPIPSVGG.random(2, widths=(16,) * 5)
     ok = torch.zeros(3, 16, 16)
     with pytest.raises(RuntimeError, match="no CPU fallback"):
@@ -262,14 +261,6 @@ def test_evaluator_without_a_net_returns_todays_keys():
 
 
 # ---- the C side without a GPU ----
-def _prototypes():
-    src = re.sub(r"/\*.*?\*/", "", open(HDR).read(), flags=re.S)
-    out = {}
-    for ret, name, args in re.findall(r"^\s*(\w+\s*\*?)\s*(texgs_\w+)\s*\(([^)]*)\)\s*;", src, flags=re.M):
-        out[name] = (ret.strip(), [a.strip() for a in args.split(",")])
-    return out
-
-
 def test_ctypes_mirrors_match_the_header(tmp_path):
     from texgs import lpips as L
     structs = {"TexGSConv3x3": L.Conv3x3Struct, "TexGSLpipsHead": L.LpipsHeadStruct}
@@ -277,45 +268,14 @@ def test_ctypes_mirrors_match_the_header(tmp_path):
               "TEXGS_CONV_TILE_W": L.TILE_W, "TEXGS_CONV_CIN_STEP": L.CIN_STEP, "TEXGS_CONV_K_STEP": L.K_STEP,
               "TEXGS_CONV_COUT_TILE": L.COUT_TILE, "TEXGS_CONV_MAX_CHANNELS": L.MAX_CHANNELS, "TEXGS_CONV_MAX_BATCH": L.MAX_BATCH,
               "TEXGS_LPIPS_ROW": L.ROW, "TEXGS_LPIPS_LAYERS": L.LAYERS, "TEXGS_LPIPS_HEAD_MAX_BLOCKS": L.HEAD_MAX_BLOCKS}
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "texgs_lpips.h"', 'int main(void) {']
-    for cname, cls in structs.items():
-        lines.append(f'printf("{cname} %zu\\n", sizeof({cname}));')
-        for fname, _ in cls._fields_:
-            lines.append(f'printf("{cname}.{fname} %zu\\n", offsetof({cname}, {fname}));')
-    for cname in consts:
-        lines.append(f'printf("{cname} %d\\n", (int)({cname}));')
-    lines.append('return 0; }')
-    src = tmp_path / "layout.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "layout"
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-pedantic", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    got = {l.split()[0]: int(l.split()[1]) for l in subprocess.check_output([str(exe)]).decode().split("\n") if l.strip()}
-    for cname, cls in structs.items():
-        assert got[cname] == ctypes.sizeof(cls), cname
-        for fname, _ in cls._fields_:
-            assert got[f"{cname}.{fname}"] == getattr(cls, fname).offset, (cname, fname)
-    for cname, value in consts.items():
-        assert got[cname] == value, cname
-    # every field of the C structs is mirrored (the struct bodies of the header, comments stripped)
-    body = re.sub(r"/\*.*?\*/", "", open(HDR).read(), flags=re.S)
-    for cname, cls in structs.items():
-        fields = re.search(r"typedef struct %s \{(.*?)\}" % cname, body, flags=re.S).group(1)
-        names = []
-        for decl in (d.strip() for d in fields.split(";")):
-            if decl:
-                parts = decl.split(",")
-                names += [re.findall(r"\w+", parts[0])[-1]] + [p.strip() for p in parts[1:]]
-        assert names == [f for f, _ in cls._fields_], cname
+    assert abi_check.layout_mismatches("texgs_lpips.h", structs, consts, tmp_path) == []
 
 
 def test_every_prototype_has_a_signature_of_the_same_arity(lib_built):
     from texgs import lpips as L
-    protos = _prototypes()
+    protos = abi_check.prototypes(HDR)
     assert sorted(protos) == sorted(L.SIGNATURES) and len(protos) == 5
-    for name, (ret, args) in protos.items():
-        restype, argtypes = L.SIGNATURES[name]
-        assert len(args) == len(argtypes), name
-        assert (restype is ctypes.c_size_t) == (ret == "size_t") and (restype is ctypes.c_int) == (ret == "int"), name
+    assert abi_check.signature_mismatches(HDR, L.SIGNATURES, {"TexGSConv3x3": L.Conv3x3Struct, "TexGSLpipsHead": L.LpipsHeadStruct}) == []
     lib = ctypes.CDLL(lib_built)
     for name in protos:
         assert hasattr(lib, name), name

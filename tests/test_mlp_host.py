@@ -19,6 +19,7 @@ import torch
 from torch import nn
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import abi_check  # noqa: E402
 import mlp_ref as R  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -95,20 +96,8 @@ def test_struct_matches_c_layout(tmp_path):
     cls = mlp.MlpStruct
     consts = {"TEXGS_MLP_WIDTH": mlp.WIDTH, "TEXGS_MLP_MAX_HIDDEN_LAYERS": mlp.MAX_HIDDEN_LAYERS, "TEXGS_MLP_FORWARD_TILE": mlp.FORWARD_TILE,
               "TEXGS_MLP_BACKWARD_TILE": mlp.BACKWARD_TILE, "TEXGS_MLP_BACKWARD_MAX_WORKGROUPS": mlp.BACKWARD_MAX_WORKGROUPS}
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "texgs_mlp.h"', 'int main(void) {', 'printf("size %zu\\n", sizeof(TexGSMlp));']
-    for fname, _ in cls._fields_:
-        lines.append(f'printf("{fname} %zu\\n", offsetof(TexGSMlp, {fname}));')
-    lines += [f'printf("{k} %d\\n", (int){k});' for k in consts] + ['return 0; }']
-    src = tmp_path / "layout.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "layout"
-    subprocess.check_call(["gcc", "-std=c99", "-I", INC, str(src), "-o", str(exe)])
-    got = dict(l.split() for l in subprocess.check_output([str(exe)]).decode().split("\n") if l.strip())
-    assert int(got["size"]) == C.sizeof(cls) == 16
-    for fname, _ in cls._fields_:
-        assert int(got[fname]) == getattr(cls, fname).offset, fname
-    assert [f for f, _ in cls._fields_] == ["n_in", "n_out", "n_hidden_layers", "n_neurons"]
-    assert {k: int(got[k]) for k in consts} == consts
+    assert abi_check.layout_mismatches("texgs_mlp.h", {"TexGSMlp": cls}, consts, tmp_path) == []
+    assert C.sizeof(cls) == 16 and [f for f, _ in cls._fields_] == ["n_in", "n_out", "n_hidden_layers", "n_neurons"]
 
 
 def test_header_is_plain_c99_and_stands_alone(tmp_path):
@@ -120,26 +109,14 @@ def test_header_is_plain_c99_and_stands_alone(tmp_path):
     assert '#include "texgs_mlp.h"' in open(os.path.join(ROOT, "texture-gs_amd", "csrc", "common.h")).read()
 
 
-def _prototypes():
-    src = re.sub(r"/\*.*?\*/", "", open(HDR).read(), flags=re.S)
-    out = {}
-    for ret, name, args in re.findall(r"^\s*(\w+)\s+(texgs_\w+)\s*\(([^)]*)\)\s*;", src, flags=re.M):
-        out[name] = (ret, [re.sub(r"\s+", "", re.sub(r"\bconst\b", "", re.sub(r"\w+$", "", a.strip()))) for a in args.split(",")])
-    return out
-
-
 def test_library_exports_the_entries_and_the_signatures_match_the_prototypes(lib_built):
     from texgs import _lib, mlp
-    protos = _prototypes()
+    protos = abi_check.prototypes(HDR)
     assert sorted(protos) == sorted(mlp.SIGNATURES) == sorted(["texgs_mlp_param_count", "texgs_mlp_forward_temp_bytes", "texgs_mlp_forward",
                                                                 "texgs_mlp_backward_temp_bytes", "texgs_mlp_backward"])
     raw = C.CDLL(lib_built)
-    ctype = {"TexGSMlp*": C.POINTER(mlp.MlpStruct), "float*": C.c_void_p, "void*": C.c_void_p, "int32_t": C.c_int32}
-    for name, (ret, args) in protos.items():
-        assert hasattr(raw, name), name
-        restype, argtypes = mlp.SIGNATURES[name]
-        assert restype is {"int": C.c_int, "size_t": C.c_size_t}[ret], name
-        assert argtypes == [ctype[a] for a in args], (name, args)
+    assert all(hasattr(raw, name) for name in protos)
+    assert abi_check.signature_mismatches(HDR, mlp.SIGNATURES, {"TexGSMlp": mlp.MlpStruct}) == []
     lib = mlp.entry()
     assert lib is _lib.load() and lib.texgs_mlp_forward.argtypes == mlp.SIGNATURES["texgs_mlp_forward"][1]
     # the mirror and the signatures live in texgs/mlp.py, not in the table that tests/test_abi.py pins to texgs.h

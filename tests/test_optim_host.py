@@ -17,6 +17,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import abi_check  # noqa: E402
 import adam_ref as R  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -70,21 +71,9 @@ def _defines():
 def test_record_matches_c_layout(tmp_path):
     from texgs import optim
     cls = optim.AdamTensor
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "texgs_optim.h"', 'int main(void) {',
-             'printf("size %zu\\n", sizeof(TexGSAdamTensor));']
-    for fname, _ in cls._fields_:
-        lines.append(f'printf("{fname} %zu\\n", offsetof(TexGSAdamTensor, {fname}));')
-    lines += ['printf("TEXGS_ADAM_MAX_TENSORS %d\\n", (int)TEXGS_ADAM_MAX_TENSORS);', 'printf("TEXGS_ADAM_CHUNK %d\\n", (int)TEXGS_ADAM_CHUNK);',
-              'return 0; }']
-    src = tmp_path / "layout.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "layout"
-    subprocess.check_call(["gcc", "-std=c99", "-I", INC, str(src), "-o", str(exe)])
-    got = dict(l.split() for l in subprocess.check_output([str(exe)]).decode().split("\n") if l.strip())
-    assert int(got["size"]) == C.sizeof(cls) == 64
-    for fname, _ in cls._fields_:
-        assert int(got[fname]) == getattr(cls, fname).offset, fname
-    assert int(got["TEXGS_ADAM_MAX_TENSORS"]) == optim.MAX_TENSORS and int(got["TEXGS_ADAM_CHUNK"]) == optim.CHUNK
+    consts = {"TEXGS_ADAM_MAX_TENSORS": optim.MAX_TENSORS, "TEXGS_ADAM_CHUNK": optim.CHUNK}
+    assert abi_check.layout_mismatches("texgs_optim.h", {"TexGSAdamTensor": cls}, consts, tmp_path) == []
+    assert C.sizeof(cls) == 64
     assert [f for f, _ in cls._fields_] == ["p", "g", "m", "v", "numel", "w1", "beta2", "w2", "bc2_sqrt", "eps", "neg_step_size"]
 
 
@@ -96,23 +85,13 @@ def test_header_is_plain_c99_and_stands_alone(tmp_path):
     assert sorted(re.findall(r"#include\s+[<\"]([^>\"]+)[>\"]", text)) == ["stddef.h", "stdint.h"]
 
 
-def _prototype():
-    src = re.sub(r"/\*.*?\*/", "", open(HDR).read(), flags=re.S)
-    (ret, name, args), = re.findall(r"^\s*(\w+)\s+(texgs_\w+)\s*\(([^)]*)\)\s*;", src, flags=re.M)
-    args = [re.sub(r"\s+", "", re.sub(r"\bconst\b", "", re.sub(r"\w+$", "", a.strip()))) for a in args.split(",")]
-    return ret, name, args
-
-
 def test_library_exports_the_entry_and_the_signature_matches_the_prototype(lib_built):
     from texgs import _lib, optim
-    ret, name, args = _prototype()
+    (name, (ret, args)), = abi_check.prototypes(HDR).items()
     assert (ret, name, args) == ("int", "texgs_adam_step", ["TexGSAdamTensor*", "int32_t", "int32_t", "void*"])
     assert hasattr(C.CDLL(lib_built), name)
     restype, argtypes = optim.SIGNATURE
-    assert restype is C.c_int and len(argtypes) == len(args)
-    assert argtypes[0] is C.POINTER(optim.AdamTensor) and argtypes[3] is C.c_void_p
-    for t in argtypes[1:3]:
-        assert C.sizeof(t) == 4 and t._type_ in "il"           # a signed 32-bit integer
+    assert abi_check.signature_mismatches(HDR, {name: optim.SIGNATURE}, {"TexGSAdamTensor": optim.AdamTensor}) == []
     fn = optim.entry()
     assert fn is _lib.load().texgs_adam_step and fn.argtypes == argtypes and fn.restype is restype
     # the mirror and the signature live in texgs/optim.py, not in the table that tests/test_abi.py pins to texgs.h
@@ -124,7 +103,7 @@ def test_a_library_without_the_symbol_is_refused_like_a_stale_one(monkeypatch):
 
     class Old:
         pass
-    monkeypatch.setattr(optim, "_fn", None)
+    monkeypatch.setattr(_lib, "_bound", {})             # no table counts as applied: entry() has to bind
     monkeypatch.setattr(_lib, "load", lambda: Old())
     with pytest.raises(RuntimeError, match=r"does not export texgs_adam_step; rebuild it with `python texture-gs_amd/build.py`"):
         optim.entry()

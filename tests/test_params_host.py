@@ -17,6 +17,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import abi_check  # noqa: E402
 import params_ref as R  # noqa: E402
 from texgs import params as _params  # noqa: E402,F401  (the feature under test: without it this file fails at import)
 
@@ -229,25 +230,7 @@ def test_structs_match_c_layout(tmp_path):
     from texgs import params
     consts = {"TEXGS_PARAMS_ROWS_PER_WORKGROUP": params.ROWS_PER_WORKGROUP}
     assert sorted(params.MIRRORS) == ["TexGSParamsActivate", "TexGSParamsActivateGrad", "TexGSParamsCovariance", "TexGSParamsCovarianceGrad"]
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "texgs_params.h"', 'int main(void) {']
-    for cname, cls in params.MIRRORS.items():
-        lines.append(f'printf("{cname} %zu\\n", sizeof({cname}));')
-        lines += [f'printf("{cname}.{f} %zu\\n", offsetof({cname}, {f}));' for f, _ in cls._fields_]
-    lines += [f'printf("{k} %d\\n", (int){k});' for k in consts] + ['return 0; }']
-    src = tmp_path / "layout.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "layout"
-    subprocess.check_call(["gcc", "-std=c99", "-I", INC, str(src), "-o", str(exe)])
-    got = dict(l.split() for l in subprocess.check_output([str(exe)]).decode().split("\n") if l.strip())
-    for cname, cls in params.MIRRORS.items():
-        assert int(got[cname]) == C.sizeof(cls), cname
-        for f, _ in cls._fields_:
-            assert int(got[f"{cname}.{f}"]) == getattr(cls, f).offset, (cname, f)
-    assert {k: int(got[k]) for k in consts} == consts
-    text = re.sub(r"/\*.*?\*/", "", open(HDR).read(), flags=re.S)
-    for cname, cls in params.MIRRORS.items():
-        body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (cname, cname), text, flags=re.S).group(1)
-        assert re.findall(r"(\w+);", body) == [f for f, _ in cls._fields_], cname
+    assert abi_check.layout_mismatches("texgs_params.h", params.MIRRORS, consts, tmp_path) == []
 
 
 def test_header_compiles_as_c_and_as_cpp_and_stands_alone(tmp_path):
@@ -267,30 +250,15 @@ def test_header_compiles_as_c_and_as_cpp_and_stands_alone(tmp_path):
         assert not re.search(r"\basm\b|__asm", open(os.path.join(CSRC, name)).read()), name
 
 
-def _prototypes():
-    src = re.sub(r"/\*.*?\*/", "", open(HDR).read(), flags=re.S)
-    out = {}
-    for ret, name, args in re.findall(r"^\s*(\w+)\s+(texgs_\w+)\s*\(([^)]*)\)\s*;", src, flags=re.M):
-        out[name] = (ret, [re.sub(r"\s+", "", re.sub(r"\bconst\b", "", re.sub(r"\w+$", "", a.strip()))) for a in args.split(",")])
-    return out
-
-
 def test_library_exports_the_entries_and_the_signatures_match_the_prototypes(lib_built):
     from texgs import _lib, params
-    protos = _prototypes()
+    protos = abi_check.prototypes(HDR)
     assert sorted(protos) == sorted(params.SIGNATURES) == sorted(
         ["texgs_params_temp_bytes", "texgs_params_activate", "texgs_params_activate_backward", "texgs_params_covariance",
          "texgs_params_covariance_backward"])
     raw = C.CDLL(lib_built)
-    ctype = {"TexGSParamsActivate*": C.POINTER(params.ParamsActivateStruct), "TexGSParamsActivateGrad*": C.POINTER(params.ParamsActivateGradStruct),
-             "TexGSParamsCovariance*": C.POINTER(params.ParamsCovarianceStruct),
-             "TexGSParamsCovarianceGrad*": C.POINTER(params.ParamsCovarianceGradStruct), "void*": C.c_void_p, "int32_t": C.c_int32,
-             "size_t": C.c_size_t}
-    for name, (ret, args) in protos.items():
-        assert hasattr(raw, name), name
-        restype, argtypes = params.SIGNATURES[name]
-        assert restype is {"int": C.c_int, "size_t": C.c_size_t}[ret], name
-        assert argtypes == [ctype[a] for a in args], (name, args)
+    assert all(hasattr(raw, name) for name in protos)
+    assert abi_check.signature_mismatches(HDR, params.SIGNATURES, params.MIRRORS) == []
     lib = params.entry()
     assert lib is _lib.load() and lib.texgs_params_activate.argtypes == params.SIGNATURES["texgs_params_activate"][1]
     assert lib.texgs_abi_version() == 19

@@ -18,6 +18,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import abi_check  # noqa: E402
 import present_ref as R  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -116,26 +117,7 @@ def test_structs_match_c_layout(tmp_path):
               "TEXGS_PRESENT_MAX_WORKGROUPS": present.MAX_WORKGROUPS, "TEXGS_PRESENT_AFFINE": present.AFFINE,
               "TEXGS_PRESENT_COMPOSITE": present.COMPOSITE, "TEXGS_PRESENT_SWAP_RB": present.SWAP_RB}
     assert sorted(present.MIRRORS) == ["TexGSCubeCross", "TexGSDepthColour", "TexGSPresent"]
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "texgs_present.h"', 'int main(void) {']
-    for cname, cls in present.MIRRORS.items():
-        lines.append(f'printf("{cname} %zu\\n", sizeof({cname}));')
-        lines += [f'printf("{cname}.{f} %zu\\n", offsetof({cname}, {f}));' for f, _ in cls._fields_]
-    lines += [f'printf("{k} %d\\n", (int){k});' for k in consts] + ['return 0; }']
-    src = tmp_path / "layout.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "layout"
-    subprocess.check_call(["gcc", "-std=c99", "-I", INC, str(src), "-o", str(exe)])
-    got = dict(l.split() for l in subprocess.check_output([str(exe)]).decode().split("\n") if l.strip())
-    for cname, cls in present.MIRRORS.items():
-        assert int(got[cname]) == C.sizeof(cls), cname
-        for f, _ in cls._fields_:
-            assert int(got[f"{cname}.{f}"]) == getattr(cls, f).offset, (cname, f)
-    assert {k: int(got[k]) for k in consts} == consts
-    # every field the header declares is mirrored, in order
-    text = re.sub(r"/\*.*?\*/", "", open(HDR).read(), flags=re.S)
-    for cname, cls in present.MIRRORS.items():
-        body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (cname, cname), text, flags=re.S).group(1)
-        assert re.findall(r"(\w+);", body) == [f for f, _ in cls._fields_], cname
+    assert abi_check.layout_mismatches("texgs_present.h", present.MIRRORS, consts, tmp_path) == []
 
 
 def test_header_is_plain_c99_and_stands_alone(tmp_path):
@@ -148,27 +130,14 @@ def test_header_is_plain_c99_and_stands_alone(tmp_path):
     assert '#include "texgs_present.h"' in open(os.path.join(ROOT, "texture-gs_amd", "csrc", "common.h")).read()
 
 
-def _prototypes():
-    src = re.sub(r"/\*.*?\*/", "", open(HDR).read(), flags=re.S)
-    out = {}
-    for ret, name, args in re.findall(r"^\s*(\w+)\s+(texgs_\w+)\s*\(([^)]*)\)\s*;", src, flags=re.M):
-        out[name] = (ret, [re.sub(r"\s+", "", re.sub(r"\bconst\b", "", re.sub(r"\w+$", "", a.strip()))) for a in args.split(",")])
-    return out
-
-
 def test_library_exports_the_entries_and_the_signatures_match_the_prototypes(lib_built):
     from texgs import _lib, present
-    protos = _prototypes()
+    protos = abi_check.prototypes(HDR)
     assert sorted(protos) == sorted(present.SIGNATURES) == sorted(["texgs_present", "texgs_depth_colour_temp_bytes", "texgs_depth_colour",
                                                                     "texgs_cube_cross"])
     raw = C.CDLL(lib_built)
-    ctype = {"TexGSPresent*": C.POINTER(present.PresentStruct), "TexGSDepthColour*": C.POINTER(present.DepthColourStruct),
-             "TexGSCubeCross*": C.POINTER(present.CubeCrossStruct), "void*": C.c_void_p, "int32_t": C.c_int32, "size_t": C.c_size_t}
-    for name, (ret, args) in protos.items():
-        assert hasattr(raw, name), name
-        restype, argtypes = present.SIGNATURES[name]
-        assert restype is {"int": C.c_int, "size_t": C.c_size_t}[ret], name
-        assert argtypes == [ctype[a] for a in args], (name, args)
+    assert all(hasattr(raw, name) for name in protos)
+    assert abi_check.signature_mismatches(HDR, present.SIGNATURES, present.MIRRORS) == []
     lib = present.entry()
     assert lib is _lib.load() and lib.texgs_present.argtypes == present.SIGNATURES["texgs_present"][1]
     # the mirrors and the signatures live in texgs/present.py, not in the table that tests/test_abi.py pins to texgs.h

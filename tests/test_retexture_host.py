@@ -18,6 +18,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import abi_check  # noqa: E402
 import retexture_ref as R  # noqa: E402
 from texgs import retexture as RT  # noqa: E402  (the feature under test: without it this file fails at import)
 from texgs import texture_io as TIO  # noqa: E402
@@ -196,39 +197,16 @@ def test_structs_match_c_layout(tmp_path):
     consts = {"TEXGS_RETEX_TEXELS_PER_THREAD": RT.TEXELS_PER_THREAD, "TEXGS_RETEX_THREADS": RT.THREADS, "TEXGS_RETEX_MAX_RES": RT.MAX_RES,
               "TEXGS_RETEX_MAX_SRC": RT.MAX_SRC, "TEXGS_RETEX_RGB": RT.ORDERS["rgb"], "TEXGS_RETEX_BGR": RT.ORDERS["bgr"]}
     assert sorted(RT.MIRRORS) == ["TexGSRetexCross", "TexGSRetexLatLong"]
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "texgs_retexture.h"', 'int main(void) {']
-    for cname, cls in RT.MIRRORS.items():
-        lines.append(f'printf("{cname} %zu\\n", sizeof({cname}));')
-        lines += [f'printf("{cname}.{f} %zu\\n", offsetof({cname}, {f}));' for f, _ in cls._fields_]
-    lines += [f'printf("{k} %d\\n", (int){k});' for k in consts] + ['return 0; }']
-    src, exe = tmp_path / "layout.c", tmp_path / "layout"
-    src.write_text("\n".join(lines))
-    subprocess.check_call(["gcc", "-std=c99", "-I", INC, str(src), "-o", str(exe)])
-    got = dict(l.split() for l in subprocess.check_output([str(exe)]).decode().split("\n") if l.strip())
-    for cname, cls in RT.MIRRORS.items():
-        assert int(got[cname]) == C.sizeof(cls), cname
-        for f, _ in cls._fields_:
-            assert int(got[f"{cname}.{f}"]) == getattr(cls, f).offset, (cname, f)
-    assert {k: int(got[k]) for k in consts} == consts
-    text = re.sub(r"/\*.*?\*/", "", open(HDR).read(), flags=re.S)
-    for cname, cls in RT.MIRRORS.items():
-        body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (cname, cname), text, flags=re.S).group(1)
-        assert re.findall(r"(\w+);", body) == [f for f, _ in cls._fields_], cname
+    assert abi_check.layout_mismatches("texgs_retexture.h", RT.MIRRORS, consts, tmp_path) == []
 
 
 def test_library_exports_the_entries_and_the_signatures_match_the_prototypes(lib_built):
     from texgs import _lib
-    src = re.sub(r"/\*.*?\*/", "", open(HDR).read(), flags=re.S)
-    protos = {}
-    for ret, name, args in re.findall(r"^\s*(\w+)\s+(texgs_\w+)\s*\(([^)]*)\)\s*;", src, flags=re.M):
-        protos[name] = (ret, [re.sub(r"\s+", "", re.sub(r"\bconst\b", "", re.sub(r"\w+$", "", a.strip()))) for a in args.split(",")])
+    protos = abi_check.prototypes(HDR)
     assert sorted(protos) == sorted(RT.SIGNATURES) == ["texgs_retexture_cross", "texgs_retexture_latlong"]
     raw = C.CDLL(lib_built)
-    ctype = {"TexGSRetexCross*": C.POINTER(RT.RetexCrossStruct), "TexGSRetexLatLong*": C.POINTER(RT.RetexLatLongStruct), "void*": C.c_void_p}
-    for name, (ret, args) in protos.items():
-        assert hasattr(raw, name), name
-        restype, argtypes = RT.SIGNATURES[name]
-        assert ret == "int" and restype is C.c_int and argtypes == [ctype[a] for a in args], (name, args)
+    assert all(hasattr(raw, name) for name in protos)
+    assert abi_check.signature_mismatches(HDR, RT.SIGNATURES, RT.MIRRORS) == []
     lib = RT.entry()
     assert lib is _lib.load() and lib.texgs_retexture_cross.argtypes == RT.SIGNATURES["texgs_retexture_cross"][1]
     assert lib.texgs_abi_version() == 19

@@ -2,10 +2,13 @@
 the record struct's layout against include/texgs_multiview.h, and ViewPipeline with a sink that lacks the new methods."""
 import ctypes
 import os
-import subprocess
+import sys
 
 import pytest
 import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import abi_check  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INC = os.path.join(ROOT, "include")
@@ -133,24 +136,16 @@ def test_pipeline_brackets_the_step_and_leaves_other_sinks_alone():
 def test_record_struct_matches_the_header(tmp_path):
     """ShFlushView (texgs/multiview.py) against TexGSShFlushView: size, offsets, the maximum; the header is plain C99 and declares
     texgs_sh_flush with the argument list of SH_FLUSH_SIGNATURE; the library exports it (cross-compiled: no GPU needed)."""
-    import re
     from texgs import _lib
     from texgs import multiview as MV
-    fields = [f for f, _ in MV.ShFlushView._fields_]
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "texgs_multiview.h"', 'int main(void) {',
-             'printf("size %zu\\n", sizeof(TexGSShFlushView));', 'printf("max %d\\n", (int)TEXGS_SH_FLUSH_MAX_VIEWS);']
-    lines += [f'printf("{f} %zu\\n", offsetof(TexGSShFlushView, {f}));' for f in fields] + ['return 0; }']
-    src = tmp_path / "layout.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "layout"
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-pedantic", "-I", INC, str(src), "-o", str(exe)])
-    got = dict(l.split() for l in subprocess.check_output([str(exe)]).decode().splitlines() if l.strip())
-    assert int(got["size"]) == ctypes.sizeof(MV.ShFlushView) == 24 and int(got["max"]) == MV.SH_FLUSH_MAX_VIEWS == 16
-    for f in fields:
-        assert int(got[f]) == getattr(MV.ShFlushView, f).offset, f
-    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(INC, "texgs_multiview.h")).read(), flags=re.S)
-    m = re.search(r"\bint\s+texgs_sh_flush\s*\(([^)]*)\)\s*;", hdr)
-    assert m and len(m.group(1).split(",")) == len(MV.SH_FLUSH_SIGNATURE[1]) == 9
+    mirrors = {"TexGSShFlushView": MV.ShFlushView}
+    assert abi_check.layout_mismatches("texgs_multiview.h", mirrors, {"TEXGS_SH_FLUSH_MAX_VIEWS": MV.SH_FLUSH_MAX_VIEWS}, tmp_path) == []
+    assert ctypes.sizeof(MV.ShFlushView) == 24 and MV.SH_FLUSH_MAX_VIEWS == 16
+    hdr = os.path.join(INC, "texgs_multiview.h")
+    assert len(abi_check.prototypes(hdr)["texgs_sh_flush"][1]) == len(MV.SH_FLUSH_SIGNATURE[1]) == 9
+    table = {"texgs_sh_flush": MV.SH_FLUSH_SIGNATURE, **MV.views_signatures()}       # the header's other entry points: the batched front end's
+    texgs_h = {"TexGSFrame": _lib.Frame, "TexGSInputs": _lib.Inputs, "TexGSGeom": _lib.Geom, "TexGSBinning": _lib.Binning, "TexGSImage": _lib.Image}
+    assert abi_check.signature_mismatches(hdr, table, {**texgs_h, **mirrors}) == []
     assert hasattr(_lib.load(), "texgs_sh_flush")
     # the new TexGSGrads field is the struct's last: a zero-filled struct of the old size means "not deferred"
     assert _lib.Grads._fields_[-1][0] == "dL_dvd_residue" and _lib.Grads._fields_[-2][0] == "accumulate"

@@ -19,6 +19,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import abi_check  # noqa: E402
 import shcolor_ref as R  # noqa: E402
 from texgs import shcolor as _shcolor  # noqa: E402,F401  (the feature under test: without it this file fails at import)
 
@@ -214,26 +215,8 @@ def test_structs_match_c_layout(tmp_path):
               "TEXGS_SH_COLORS_MAX_DEGREE": shcolor.MAX_DEGREE, "TEXGS_SH_COLORS": shcolor.MODE_COLORS, "TEXGS_SH_EVAL": shcolor.MODE_EVAL,
               "TEXGS_SH_LAYOUT_KC": shcolor.LAYOUT_KC, "TEXGS_SH_LAYOUT_CK": shcolor.LAYOUT_CK}
     assert sorted(shcolor.MIRRORS) == ["TexGSShColorGradView", "TexGSShColorView", "TexGSShColors", "TexGSShColorsGrad"]
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "texgs_shcolor.h"', 'int main(void) {']
-    for cname, cls in shcolor.MIRRORS.items():
-        lines.append(f'printf("{cname} %zu\\n", sizeof({cname}));')
-        lines += [f'printf("{cname}.{f} %zu\\n", offsetof({cname}, {f}));' for f, _ in cls._fields_]
-    lines += [f'printf("{k} %d\\n", (int){k});' for k in consts] + ['return 0; }']
-    src = tmp_path / "layout.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "layout"
-    subprocess.check_call(["gcc", "-std=c99", "-I", INC, str(src), "-o", str(exe)])
-    got = dict(l.split() for l in subprocess.check_output([str(exe)]).decode().split("\n") if l.strip())
-    for cname, cls in shcolor.MIRRORS.items():
-        assert int(got[cname]) == C.sizeof(cls), cname
-        for f, _ in cls._fields_:
-            assert int(got[f"{cname}.{f}"]) == getattr(cls, f).offset, (cname, f)
-    assert {k: int(got[k]) for k in consts} == consts
+    assert abi_check.layout_mismatches("texgs_shcolor.h", shcolor.MIRRORS, consts, tmp_path) == []
     assert C.sizeof(shcolor.ShColorViewStruct) == C.sizeof(shcolor.ShColorGradViewStruct) == 16
-    text = re.sub(r"/\*.*?\*/", "", open(HDR).read(), flags=re.S)
-    for cname, cls in shcolor.MIRRORS.items():
-        body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (cname, cname), text, flags=re.S).group(1)
-        assert re.findall(r"(\w+);", body) == [f for f, _ in cls._fields_], cname
 
 
 def test_header_compiles_as_c_and_as_cpp_and_stands_alone(tmp_path):
@@ -253,27 +236,13 @@ def test_header_compiles_as_c_and_as_cpp_and_stands_alone(tmp_path):
         assert not re.search(r"\basm\b|__asm|atomic", open(os.path.join(CSRC, name)).read()), name
 
 
-def _prototypes():
-    src = re.sub(r"/\*.*?\*/", "", open(HDR).read(), flags=re.S)
-    out = {}
-    for ret, name, args in re.findall(r"^\s*(\w+)\s+(texgs_\w+)\s*\(([^)]*)\)\s*;", src, flags=re.M):
-        out[name] = (ret, [re.sub(r"\s+", "", re.sub(r"\bconst\b", "", re.sub(r"\w+$", "", a.strip()))) for a in args.split(",")])
-    return out
-
-
 def test_library_exports_the_entries_and_the_signatures_match_the_prototypes(lib_built):
     from texgs import _lib, shcolor
-    protos = _prototypes()
+    protos = abi_check.prototypes(HDR)
     assert sorted(protos) == sorted(shcolor.SIGNATURES) == ["texgs_sh_colors_backward", "texgs_sh_colors_forward"]
     raw = C.CDLL(lib_built)
-    ctype = {"TexGSShColors*": C.POINTER(shcolor.ShColorsStruct), "TexGSShColorsGrad*": C.POINTER(shcolor.ShColorsGradStruct),
-             "TexGSShColorView*": C.POINTER(shcolor.ShColorViewStruct), "TexGSShColorGradView*": C.POINTER(shcolor.ShColorGradViewStruct),
-             "void*": C.c_void_p, "int32_t": C.c_int32}
-    for name, (ret, args) in protos.items():
-        assert hasattr(raw, name), name
-        restype, argtypes = shcolor.SIGNATURES[name]
-        assert restype is {"int": C.c_int}[ret], name
-        assert argtypes == [ctype[a] for a in args], (name, args)
+    assert all(hasattr(raw, name) for name in protos)
+    assert abi_check.signature_mismatches(HDR, shcolor.SIGNATURES, shcolor.MIRRORS) == []
     lib = shcolor.entry()
     assert lib is _lib.load() and lib.texgs_sh_colors_forward.argtypes == shcolor.SIGNATURES["texgs_sh_colors_forward"][1]
     assert lib.texgs_abi_version() == 19

@@ -16,6 +16,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import abi_check  # noqa: E402
 import surface_ref as R  # noqa: E402
 from texgs import surface as _surface  # noqa: E402,F401  (the feature under test: without it this file fails at import)
 
@@ -125,25 +126,7 @@ def test_structs_match_c_layout(tmp_path):
     consts = {"TEXGS_SURFACE_PIXELS_PER_THREAD": surface.PIXELS_PER_THREAD, "TEXGS_SURFACE_PIXELS_PER_WORKGROUP": surface.PIXELS_PER_WORKGROUP,
               "TEXGS_SURFACE_SCAN_WIDTH": surface.SCAN_WIDTH, "TEXGS_SURFACE_MAX_SIDE": surface.MAX_SIDE}
     assert sorted(surface.MIRRORS) == ["TexGSSurfaceCompose", "TexGSSurfacePoints"]
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "texgs_surface.h"', 'int main(void) {']
-    for cname, cls in surface.MIRRORS.items():
-        lines.append(f'printf("{cname} %zu\\n", sizeof({cname}));')
-        lines += [f'printf("{cname}.{f} %zu\\n", offsetof({cname}, {f}));' for f, _ in cls._fields_]
-    lines += [f'printf("{k} %d\\n", (int){k});' for k in consts] + ['return 0; }']
-    src = tmp_path / "layout.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "layout"
-    subprocess.check_call(["gcc", "-std=c99", "-I", INC, str(src), "-o", str(exe)])
-    got = dict(l.split() for l in subprocess.check_output([str(exe)]).decode().split("\n") if l.strip())
-    for cname, cls in surface.MIRRORS.items():
-        assert int(got[cname]) == C.sizeof(cls), cname
-        for f, _ in cls._fields_:
-            assert int(got[f"{cname}.{f}"]) == getattr(cls, f).offset, (cname, f)
-    assert {k: int(got[k]) for k in consts} == consts
-    text = re.sub(r"/\*.*?\*/", "", open(HDR).read(), flags=re.S)
-    for cname, cls in surface.MIRRORS.items():
-        body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (cname, cname), text, flags=re.S).group(1)
-        assert re.findall(r"(\w+);", body) == [f for f, _ in cls._fields_], cname
+    assert abi_check.layout_mismatches("texgs_surface.h", surface.MIRRORS, consts, tmp_path) == []
 
 
 def test_header_is_plain_c99_and_stands_alone(tmp_path):
@@ -157,26 +140,13 @@ def test_header_is_plain_c99_and_stands_alone(tmp_path):
     assert re.search(r"#define TEXGS_ABI_VERSION 19\b", open(os.path.join(INC, "texgs.h")).read())
 
 
-def _prototypes():
-    src = re.sub(r"/\*.*?\*/", "", open(HDR).read(), flags=re.S)
-    out = {}
-    for ret, name, args in re.findall(r"^\s*(\w+)\s+(texgs_\w+)\s*\(([^)]*)\)\s*;", src, flags=re.M):
-        out[name] = (ret, [re.sub(r"\s+", "", re.sub(r"\bconst\b", "", re.sub(r"\w+$", "", a.strip()))) for a in args.split(",")])
-    return out
-
-
 def test_library_exports_the_entries_and_the_signatures_match_the_prototypes(lib_built):
     from texgs import _lib, surface
-    protos = _prototypes()
+    protos = abi_check.prototypes(HDR)
     assert sorted(protos) == sorted(surface.SIGNATURES) == sorted(["texgs_surface_temp_bytes", "texgs_surface_points", "texgs_surface_compose"])
     raw = C.CDLL(lib_built)
-    ctype = {"TexGSSurfacePoints*": C.POINTER(surface.SurfacePointsStruct), "TexGSSurfaceCompose*": C.POINTER(surface.SurfaceComposeStruct),
-             "void*": C.c_void_p, "int32_t": C.c_int32, "size_t": C.c_size_t}
-    for name, (ret, args) in protos.items():
-        assert hasattr(raw, name), name
-        restype, argtypes = surface.SIGNATURES[name]
-        assert restype is {"int": C.c_int, "size_t": C.c_size_t}[ret], name
-        assert argtypes == [ctype[a] for a in args], (name, args)
+    assert all(hasattr(raw, name) for name in protos)
+    assert abi_check.signature_mismatches(HDR, surface.SIGNATURES, surface.MIRRORS) == []
     lib = surface.entry()
     assert lib is _lib.load() and lib.texgs_surface_points.argtypes == surface.SIGNATURES["texgs_surface_points"][1]
     assert lib.texgs_abi_version() == 19

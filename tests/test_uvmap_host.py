@@ -1,6 +1,5 @@
 """-m "not gpu": the UV-map stage's host side -- the hash-grid statement (level table, dense / hashed corners, the x = 1 wrap, its
 input gradient), the tiny-cuda-nn state loader of InvUVNet, loud failure on CPU tensors, the C layout of the new struct."""
-import ctypes
 import math
 import os
 import subprocess
@@ -11,6 +10,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import abi_check  # noqa: E402
 import hashgrid_ref as R  # noqa: E402
 
 
@@ -265,17 +265,5 @@ def test_uvmap_does_not_import_oracle_or_tests():
 def test_hashgrid_struct_matches_c_layout(tmp_path):
     sys.path.insert(0, os.path.join(ROOT, "texture-gs_amd"))
     from texgs import _lib
-    cls = _lib.HashGridStruct
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "texgs.h"', 'int main(void) {',
-             'printf("size %zu\\n", sizeof(TexGSHashGrid));']
-    lines += [f'printf("{f} %zu\\n", offsetof(TexGSHashGrid, {f}));' for f, _ in cls._fields_]
-    lines += ['printf("consts %d %d\\n", TEXGS_HASHGRID_MAX_LEVELS, TEXGS_HASHGRID_FEATURES);', 'return 0; }']
-    src = tmp_path / "hg.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "hg"
-    subprocess.check_call(["gcc", "-std=c99", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    got = {l.split()[0]: l.split()[1:] for l in subprocess.check_output([str(exe)]).decode().splitlines() if l.strip()}
-    assert int(got["size"][0]) == ctypes.sizeof(cls)
-    for f, _ in cls._fields_:
-        assert int(got[f][0]) == getattr(cls, f).offset, f
-    assert [int(v) for v in got["consts"]] == [_lib.HASHGRID_MAX_LEVELS, _lib.HASHGRID_FEATURES]
+    consts = {"TEXGS_HASHGRID_MAX_LEVELS": _lib.HASHGRID_MAX_LEVELS, "TEXGS_HASHGRID_FEATURES": _lib.HASHGRID_FEATURES}
+    assert abi_check.layout_mismatches("texgs.h", {"TexGSHashGrid": _lib.HashGridStruct}, consts, tmp_path) == []

@@ -102,8 +102,9 @@ UV_PRECISION = {"fp32": 0, "bf16x3": 1, "mixed": 2}          # TEXGS_UV_FP32 / _
 _P = C.POINTER
 _i32, _u32, _f32, _size, _vp = C.c_int32, C.c_uint32, C.c_float, C.c_size_t, C.c_void_p
 _frame5 = [_P(Frame), _P(Inputs), _P(Geom), _P(Binning), _P(Image)]
-# The C ABI, stated once: name -> (restype, argtypes), in the order of include/texgs.h (tests/test_abi.py compares every entry with the
-# header's prototype).  load() applies it; EXPORTS is its key list.
+# The C ABI of include/texgs.h, stated once: name -> (restype, argtypes), in the header's order (tests/test_abi.py compares every entry
+# with the header's prototype through tests/abi_check.py, as each stage's test does for the stage's own table).  load() applies it;
+# EXPORTS is its key list.
 SIGNATURES = {
     "texgs_abi_version": (C.c_int, []),
     "texgs_build_id": (C.c_char_p, []),
@@ -160,6 +161,28 @@ KERNEL_NAMES = ["preprocess_fwd", "scan", "duplicate", "sort", "ranges", "render
                 "texgrad_reduce"]
 
 _lib = None
+_bound = {}         # id(table) -> table, for every table that bind() has applied (holding the table keeps its id from being reused)
+
+
+def _apply(lib, signatures):
+    """Set restype / argtypes of every entry of a {name: (restype, argtypes)} table on `lib`; every name that `lib` lacks is reported"""
+    missing = [n for n in signatures if not hasattr(lib, n)]
+    if missing:         # a library from before an additive change of the ABI (the version number stays): same advice as a stale version
+        raise RuntimeError(f"libtexgs.so at {LIB_PATH} does not export {', '.join(missing)}; rebuild it with "
+                           "`python texture-gs_amd/build.py`")
+    for name, (restype, argtypes) in signatures.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
+
+
+def bind(signatures):
+    """The loaded library with a stage's own table applied: {name: (restype, argtypes)}, stated in the stage's module beside its struct
+    mirrors (tests/abi_check.py compares it with the stage's header).  The table object is remembered, so every later call is one
+    lookup."""
+    if id(signatures) not in _bound:
+        _apply(load(), signatures)
+        _bound[id(signatures)] = signatures
+    return _lib
 
 
 def load():
@@ -172,13 +195,7 @@ def load():
             f"libtexgs.so not found at {LIB_PATH}: build it with `python texture-gs_amd/build.py` "
             "(hipcc --offload-arch=gfx950). There is no CPU fallback for the rasterizer.")
     lib = C.CDLL(LIB_PATH)
-    missing = [n for n in EXPORTS if not hasattr(lib, n)]
-    if missing:         # a library from before an additive change of the ABI (the version number stays): same advice as a stale version
-        raise RuntimeError(f"libtexgs.so at {LIB_PATH} does not export {', '.join(missing)}; rebuild it with "
-                           "`python texture-gs_amd/build.py`")
-    for name, (restype, argtypes) in SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = restype, argtypes
+    _apply(lib, SIGNATURES)
     v = lib.texgs_abi_version()
     if v != ABI_VERSION:
         # (no bypass in the shipped loader -- the struct layouts differ between versions; experiment scripts that A/B an

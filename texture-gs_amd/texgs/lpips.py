@@ -85,23 +85,11 @@ SIGNATURES = {
     "texgs_lpips_head_temp_bytes": (_size, [_i32, _i32, _i32]),
     "texgs_lpips_head": (C.c_int, [C.POINTER(LpipsHeadStruct), _vp]),
 }
-_lib_ready = None
 
 
 def entry():
     """The loaded library with the signatures above applied (on first use)"""
-    global _lib_ready
-    if _lib_ready is None:
-        lib = _lib.load()
-        missing = [n for n in SIGNATURES if not hasattr(lib, n)]
-        if missing:
-            raise RuntimeError(f"libtexgs.so at {_lib.LIB_PATH} does not export {', '.join(missing)}; rebuild it with "
-                               "`python texture-gs_amd/build.py`")
-        for name, (restype, argtypes) in SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = restype, argtypes
-        _lib_ready = lib
-    return _lib_ready
+    return _lib.bind(SIGNATURES)
 
 
 def _precision(precision):

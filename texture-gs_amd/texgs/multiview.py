@@ -17,6 +17,8 @@ from typing import List, Sequence
 
 import torch
 
+from . import _lib
+
 SH_FLUSH_MAX_VIEWS = 16         # TEXGS_SH_FLUSH_MAX_VIEWS: view records of one texgs_sh_flush launch
 
 
@@ -29,41 +31,29 @@ class ShFlushView(C.Structure):
 #  float* dL_dmeans3D, const TexGSShFlushView* views, int32_t count, void* stream)`
 SH_FLUSH_SIGNATURE = (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ShFlushView), C.c_int32,
                                 C.c_void_p])
-_sh_flush_fn = None
+_SH_FLUSH_SIGNATURES = {"texgs_sh_flush": SH_FLUSH_SIGNATURE}
 
 
 def sh_flush_entry():
     """texgs_sh_flush of the loaded library with its signature applied (on first use)"""
-    global _sh_flush_fn
-    if _sh_flush_fn is None:
-        from . import _lib
-        lib = _lib.load()
-        if not hasattr(lib, "texgs_sh_flush"):
-            raise RuntimeError(f"libtexgs.so at {_lib.LIB_PATH} does not export texgs_sh_flush; rebuild it with "
-                               "`python texture-gs_amd/build.py`")
-        fn = lib.texgs_sh_flush
-        fn.restype, fn.argtypes = SH_FLUSH_SIGNATURE
-        _sh_flush_fn = fn
-    return _sh_flush_fn
+    return _lib.bind(_SH_FLUSH_SIGNATURES).texgs_sh_flush
 
 
 BATCH_MAX_VIEWS = 16            # TEXGS_BATCH_MAX_VIEWS: views of one batched front end (K1..K5 once per step, texgs.rasterizer.batched_prefetch)
+_P = C.POINTER
+_VIEWS_SIGNATURES = {
+    "texgs_preprocess_forward_views": (C.c_int, [_P(_lib.Frame), _P(_lib.Inputs), _P(_lib.Geom), C.c_int32, C.c_void_p, C.c_void_p]),
+    "texgs_depth_sort_scan_views": (C.c_int, [_P(_lib.Geom), C.c_int32, C.c_int32, C.c_void_p]),
+    "texgs_bin_sort_views": (C.c_int, [_P(_lib.Frame), _P(_lib.Geom), _P(_lib.Binning), _P(_lib.Image), C.c_int32, C.c_void_p]),
+    "texgs_render_forward_binned": (C.c_int, [_P(_lib.Frame), _P(_lib.Inputs), _P(_lib.Geom), _P(_lib.Binning), _P(_lib.Image), C.c_void_p]),
+}
+_views_fns = None
 
 
 def views_signatures():
     """name -> (restype, argtypes) of the batched front end's entry points (include/texgs_multiview.h), in the header's order; the structs
     are texgs.h's, passed as arrays of `count` elements"""
-    from . import _lib
-    P, vp, i32 = C.POINTER, C.c_void_p, C.c_int32
-    return {
-        "texgs_preprocess_forward_views": (C.c_int, [P(_lib.Frame), P(_lib.Inputs), P(_lib.Geom), i32, vp, vp]),
-        "texgs_depth_sort_scan_views": (C.c_int, [P(_lib.Geom), i32, i32, vp]),
-        "texgs_bin_sort_views": (C.c_int, [P(_lib.Frame), P(_lib.Geom), P(_lib.Binning), P(_lib.Image), i32, vp]),
-        "texgs_render_forward_binned": (C.c_int, [P(_lib.Frame), P(_lib.Inputs), P(_lib.Geom), P(_lib.Binning), P(_lib.Image), vp]),
-    }
-
-
-_views_fns = None
+    return _VIEWS_SIGNATURES
 
 
 def views_entries():
@@ -71,17 +61,8 @@ def views_entries():
     global _views_fns
     if _views_fns is None:
         from types import SimpleNamespace
-        from . import _lib
-        lib = _lib.load()
-        fns = {}
-        for name, (restype, argtypes) in views_signatures().items():
-            if not hasattr(lib, name):
-                raise RuntimeError(f"libtexgs.so at {_lib.LIB_PATH} does not export {name}; rebuild it with "
-                                   "`python texture-gs_amd/build.py`")
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = restype, argtypes
-            fns[name[len("texgs_"):]] = fn
-        _views_fns = SimpleNamespace(**fns)
+        lib = _lib.bind(_VIEWS_SIGNATURES)
+        _views_fns = SimpleNamespace(**{name[len("texgs_"):]: getattr(lib, name) for name in _VIEWS_SIGNATURES})
     return _views_fns
 
 
@@ -206,7 +187,6 @@ class GradBucket:
         self._residues_used = {}
         if not pending:
             return
-        from . import _lib
         fn = sh_flush_entry()
         k = 0
         while k < len(pending):

@@ -39,21 +39,12 @@ class AdamTensor(C.Structure):
 
 # the entry point's signature: (restype, argtypes) of `int texgs_adam_step(const TexGSAdamTensor*, int32_t, int32_t, void*)`
 SIGNATURE = (C.c_int, [C.POINTER(AdamTensor), C.c_int32, C.c_int32, C.c_void_p])
-_fn = None
+_SIGNATURES = {"texgs_adam_step": SIGNATURE}
 
 
 def entry():
     """texgs_adam_step of the loaded library with its signature applied (on first use)"""
-    global _fn
-    if _fn is None:
-        lib = _lib.load()
-        if not hasattr(lib, "texgs_adam_step"):
-            raise RuntimeError(f"libtexgs.so at {_lib.LIB_PATH} does not export texgs_adam_step; rebuild it with "
-                               "`python texture-gs_amd/build.py`")
-        fn = lib.texgs_adam_step
-        fn.restype, fn.argtypes = SIGNATURE
-        _fn = fn
-    return _fn
+    return _lib.bind(_SIGNATURES).texgs_adam_step
 
 
 def scalars(step, lr, betas, eps):

@@ -65,25 +65,13 @@ SIGNATURES = {
     "texgs_params_covariance": (C.c_int, [C.POINTER(ParamsCovarianceStruct), _vp]),
     "texgs_params_covariance_backward": (C.c_int, [C.POINTER(ParamsCovarianceGradStruct), _vp]),
 }
-_lib_ready = None
 # how often each backward entry point was called from this layer (tests count them: one per backward, however many consumers)
 BACKWARD_CALLS = {"activate": 0, "covariance": 0}
 
 
 def entry():
     """The loaded library with the signatures above applied (on first use)"""
-    global _lib_ready
-    if _lib_ready is None:
-        lib = _lib.load()
-        missing = [n for n in SIGNATURES if not hasattr(lib, n)]
-        if missing:
-            raise RuntimeError(f"libtexgs.so at {_lib.LIB_PATH} does not export {', '.join(missing)}; rebuild it with "
-                               "`python texture-gs_amd/build.py`")
-        for name, (restype, argtypes) in SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = restype, argtypes
-        _lib_ready = lib
-    return _lib_ready
+    return _lib.bind(SIGNATURES)
 
 
 # ---- validation: everything a launch relies on, before any library call ----

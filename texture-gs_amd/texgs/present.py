@@ -56,23 +56,11 @@ SIGNATURES = {
     "texgs_depth_colour": (C.c_int, [C.POINTER(DepthColourStruct), _vp, _size, _vp]),
     "texgs_cube_cross": (C.c_int, [C.POINTER(CubeCrossStruct), _vp]),
 }
-_lib_ready = None
 
 
 def entry():
     """The loaded library with the signatures above applied (on first use)"""
-    global _lib_ready
-    if _lib_ready is None:
-        lib = _lib.load()
-        missing = [n for n in SIGNATURES if not hasattr(lib, n)]
-        if missing:
-            raise RuntimeError(f"libtexgs.so at {_lib.LIB_PATH} does not export {', '.join(missing)}; rebuild it with "
-                               "`python texture-gs_amd/build.py`")
-        for name, (restype, argtypes) in SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = restype, argtypes
-        _lib_ready = lib
-    return _lib_ready
+    return _lib.bind(SIGNATURES)
 
 
 # ---- validation: everything a launch relies on, before any library call ----

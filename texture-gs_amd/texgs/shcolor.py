@@ -71,25 +71,13 @@ SIGNATURES = {
     "texgs_sh_colors_forward": (C.c_int, [C.POINTER(ShColorsStruct), C.POINTER(ShColorViewStruct), _i32, _vp]),
     "texgs_sh_colors_backward": (C.c_int, [C.POINTER(ShColorsGradStruct), C.POINTER(ShColorGradViewStruct), _i32, _vp]),
 }
-_lib_ready = None
 # how often each entry point was called from this layer (tests count them: one per 16 views)
 CALLS = {"forward": 0, "backward": 0}
 
 
 def entry():
     """The loaded library with the signatures above applied (on first use)"""
-    global _lib_ready
-    if _lib_ready is None:
-        lib = _lib.load()
-        missing = [n for n in SIGNATURES if not hasattr(lib, n)]
-        if missing:
-            raise RuntimeError(f"libtexgs.so at {_lib.LIB_PATH} does not export {', '.join(missing)}; rebuild it with "
-                               "`python texture-gs_amd/build.py`")
-        for name, (restype, argtypes) in SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = restype, argtypes
-        _lib_ready = lib
-    return _lib_ready
+    return _lib.bind(SIGNATURES)
 
 
 # ---- validation: everything a launch relies on, before any library call ----
