@@ -61,7 +61,7 @@ HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "wave_ops.h"), os.
            os.path.join(ROOT, "include", "texgs_lpips_grad.h"), os.path.join(ROOT, "include", "texgs_params.h"),
            os.path.join(CSRC, "params_math.h"), os.path.join(ROOT, "include", "texgs_retexture.h"),
            os.path.join(CSRC, "retexture_math.h"), os.path.join(ROOT, "include", "texgs_shcolor.h"),
-           os.path.join(CSRC, "shcolor_math.h")]
+           os.path.join(CSRC, "shcolor_math.h"), os.path.join(CSRC, "texrec_math.h")]
 
 
 def build_id():

@@ -32,6 +32,7 @@
 // No MFMA: there is no dense contraction on this path.
 #include "common.h"
 #include "wave_ops.h"
+#include "texrec_math.h"
 
 namespace {
 
@@ -592,8 +593,13 @@ __device__ __forceinline__ void scatter_direct(float* __restrict__ dtex, uint32_
 //   w0 = low 16 bits of fx18 | low 16 bits of fy18 << 16          fx18 = round(fx * 2^18), 18 bits (as the 20-byte record kept)
 //   w1 = r, its 5 low mantissa bits replaced by the footprint's cell x inside its 32x32-texel bin (r rounded to 18 mantissa bits)
 //   w2 = g, likewise with cell y          w3 = b, its 4 low mantissa bits = the two high bits of fx18 and of fy18
-// inf / NaN survive the rounding (an inf / NaN upstream gradient still reaches exactly the texels it touches).
-struct __attribute__((aligned(16))) Rec4 { uint32_t a, b, c, d; };
+// Finite values round to nearest, ties away from zero (next to overflow: to inf); inf stays inf and every NaN stays a NaN (an inf /
+// NaN upstream gradient still reaches exactly the texels it touches).  The codec itself is csrc/texrec_math.h, host and device.
+using texrec_math::Rec4;
+using texrec_math::RecVal;
+using texrec_math::rec_word0;
+using texrec_math::rec_pack;
+using texrec_math::rec_unpack;
 __device__ __forceinline__ void rec_store(uint32_t* __restrict__ base, uint32_t slot, const Rec4 r) {
     tg_u4 v; v.x = r.a; v.y = r.b; v.z = r.c; v.w = r.d;
     __builtin_nontemporal_store(v, reinterpret_cast<tg_u4*>(base) + slot);
@@ -601,28 +607,6 @@ __device__ __forceinline__ void rec_store(uint32_t* __restrict__ base, uint32_t 
 __device__ __forceinline__ Rec4 rec_load(const Rec4* __restrict__ p) {
     const tg_u4 v = __builtin_nontemporal_load(reinterpret_cast<const tg_u4*>(p));
     Rec4 r; r.a = v.x; r.b = v.y; r.c = v.z; r.d = v.w;
-    return r;
-}
-__device__ __forceinline__ uint32_t rec_word0(float fx, float fy, uint32_t& hi) {
-    const uint32_t qx = min((uint32_t)(fx * 262144.0f + 0.5f), 262143u), qy = min((uint32_t)(fy * 262144.0f + 0.5f), 262143u);
-    hi = (qx >> 16) | ((qy >> 16) << 2);
-    return (qx & 0xFFFFu) | (qy << 16);
-}
-__device__ __forceinline__ Rec4 rec_pack(uint32_t w0, uint32_t hi, int cx, int cy, float x0, float x1, float x2) {
-    Rec4 r;
-    r.a = w0;
-    r.b = ((__float_as_uint(x0) + 16u) & ~31u) | (uint32_t)(cx & 31);
-    r.c = ((__float_as_uint(x1) + 16u) & ~31u) | (uint32_t)(cy & 31);
-    r.d = ((__float_as_uint(x2) + 8u) & ~15u) | hi;
-    return r;
-}
-struct RecVal { int cx, cy; float fx, fy, x0, x1, x2; };
-__device__ __forceinline__ RecVal rec_unpack(const Rec4 w) {
-    RecVal r;
-    r.fx = (float)((w.a & 0xFFFFu) | ((w.d & 3u) << 16)) * (1.0f / 262144.0f);
-    r.fy = (float)((w.a >> 16) | (((w.d >> 2) & 3u) << 16)) * (1.0f / 262144.0f);
-    r.cx = (int)(w.b & 31u); r.cy = (int)(w.c & 31u);
-    r.x0 = __uint_as_float(w.b & ~31u); r.x1 = __uint_as_float(w.c & ~31u); r.x2 = __uint_as_float(w.d & ~15u);
     return r;
 }
 
@@ -769,27 +753,22 @@ k_texgrad_reduce(int R, TexBinArgs tb, float* __restrict__ dtex) {
         }
         return;
     }
-    const float bound = TG_SH_C0 * __uint_as_float(bbits);
-    int e = 0;
-    (void)frexpf(bound, &e);                                   // bound < 2^e
-    const double up = (double)ldexpf(1.0f, 42 - e);
-    const float down = ldexpf(1.0f, e - 42);
-    // float -> int64 without the 11-instruction generic conversion: |v| < 2^42, so v + 1.5 * 2^52 (exact in double) carries
-    // round(v) in its mantissa; subtracting the bias as integers leaves the two's-complement value
-    const double magic = 6755399441055744.0;
-    const long long magic_bits = __double_as_longlong(magic);
+    // 2^(e-1) <= C0 * max|dL/dpixel colour| < 2^e; up = 2^(42-e) and down = 2^(e-42) as doubles: every finite bound has a scale
+    // (texrec_math.h; once per workgroup)
+    const texrec_math::Scale sc = texrec_math::scale_of(bbits);
+    const double up = sc.up, down = sc.down;
     auto add_record = [&](const Rec4 w) {
         const RecVal r = rec_unpack(w);
         const float fx = r.fx, fy = r.fy;
         const double dx0 = (double)r.x0 * up, dx1 = (double)r.x1 * up, dx2 = (double)r.x2 * up;
-        const double w00 = (double)((1.f - fx) * (1.f - fy)), w01 = (double)(fx * (1.f - fy));
-        const double w10 = (double)((1.f - fx) * fy), w11 = (double)(fx * fy);
+        double wt[4];
+        texrec_math::tap_weights(fx, fy, wt);
         ull* t = reinterpret_cast<ull*>(s_tile) + (r.cy * TB_ROW + r.cx) * 3;
-#define TB_ADD(P, V) atomicAdd((P), (ull)(__double_as_longlong((V) + magic) - magic_bits))
-        TB_ADD(t + 0, w00 * dx0); TB_ADD(t + 1, w00 * dx1); TB_ADD(t + 2, w00 * dx2);
-        TB_ADD(t + 3, w01 * dx0); TB_ADD(t + 4, w01 * dx1); TB_ADD(t + 5, w01 * dx2);
-        TB_ADD(t + TB_ROW * 3 + 0, w10 * dx0); TB_ADD(t + TB_ROW * 3 + 1, w10 * dx1); TB_ADD(t + TB_ROW * 3 + 2, w10 * dx2);
-        TB_ADD(t + TB_ROW * 3 + 3, w11 * dx0); TB_ADD(t + TB_ROW * 3 + 4, w11 * dx1); TB_ADD(t + TB_ROW * 3 + 5, w11 * dx2);
+#define TB_ADD(P, W, V) atomicAdd((P), (ull)texrec_math::to_fixed((W), (V)))
+        TB_ADD(t + 0, wt[0], dx0); TB_ADD(t + 1, wt[0], dx1); TB_ADD(t + 2, wt[0], dx2);
+        TB_ADD(t + 3, wt[1], dx0); TB_ADD(t + 4, wt[1], dx1); TB_ADD(t + 5, wt[1], dx2);
+        TB_ADD(t + TB_ROW * 3 + 0, wt[2], dx0); TB_ADD(t + TB_ROW * 3 + 1, wt[2], dx1); TB_ADD(t + TB_ROW * 3 + 2, wt[2], dx2);
+        TB_ADD(t + TB_ROW * 3 + 3, wt[3], dx0); TB_ADD(t + TB_ROW * 3 + 4, wt[3], dx1); TB_ADD(t + TB_ROW * 3 + 5, wt[3], dx2);
 #undef TB_ADD
     };
     for (uint32_t s0 = 0u; s0 < cnt; s0 += TB_SEG) {             // one trip unless the list is longer than 2^20 records
@@ -813,7 +792,7 @@ k_texgrad_reduce(int R, TexBinArgs tb, float* __restrict__ dtex) {
             const int y = by * 32 + row, xq = bx * 96 + c;
             if (y >= R || xq >= R * 3) continue;
             // rows / columns 0 and 32 of the tile are shared with the neighbouring bins' tiles, hence atomics
-            unsafeAtomicAdd(dtex + ((size_t)(face * R + y) * R) * 3 + xq, (float)q * down);
+            unsafeAtomicAdd(dtex + ((size_t)(face * R + y) * R) * 3 + xq, texrec_math::from_fixed(q, down));
         }
         __syncthreads();
     }
