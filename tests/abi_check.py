@@ -97,3 +97,26 @@ def layout_mismatches(header_name, mirrors, consts, tmp_path):
             bad.append(f"{cname}: the header's fields are {struct_fields(os.path.join(INC, header_name), cname)}, the mirror's {names}")
     bad += [f"{k}: the header has {got[k]}, the host {v}" for k, v in consts.items() if got[k] != v]
     return bad
+
+
+def build_script():
+    """texture-gs_amd/build.py as a module, imported the way texgs/_lib.py tree_build_id() imports it"""
+    import importlib.util
+    path = os.path.join(os.path.dirname(INC), "texture-gs_amd", "build.py")
+    spec = importlib.util.spec_from_file_location("texgs_build_script", path)
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def build_knows_header(header_path):
+    """The build script with `header_path` checked against what the build uses: the header is in the one list HEADERS, the rebuild rule
+    (build) and build_id() both read that list, and build_id() depends on the header being in it."""
+    build = build_script()
+    header_path = os.path.abspath(header_path)
+    assert header_path in build.HEADERS and build.HEADERS == sorted(set(build.HEADERS)), header_path
+    assert "HEADERS" in build.build.__code__.co_names and "HEADERS" in build.build_id.__code__.co_names
+    with_it = build.build_id()
+    build.HEADERS = [h for h in build.HEADERS if h != header_path]
+    assert build.build_id() != with_it, "build_id() does not read " + header_path
+    return build_script()

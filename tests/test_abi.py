@@ -233,3 +233,77 @@ def test_texture_resolution_limit_is_checked_before_any_launch(lib_built):
         assert b"tex_res > 7168" in lib.texgs_last_error() and b"32-bit byte offsets" in lib.texgs_last_error()
     with pytest.raises(RuntimeError, match=r"texgs_render_forward failed .*tex_res > 7168"):
         _lib.call(lib.texgs_render_forward, C.byref(frame(7169, 5)), C.byref(inputs), C.byref(geom), C.byref(binning), C.byref(image), None)
+
+
+def test_every_unit_refuses_into_the_one_error_string(lib_built):
+    """Each unit that defines entry points refuses one call before any launch (no GPU is needed: nothing reads the stand-in buffer),
+    with a non-zero code and its own text in texgs_last_error().  The error string is abi.hip's alone: the calls go through the units
+    forwards and then backwards, every text differs from the one before it, so a unit that wrote to a copy of its own would be seen."""
+    import ctypes as C
+    raw = C.CDLL(lib_built)
+    raw.texgs_last_error.restype = C.c_char_p
+    buf = (C.c_float * 64)()
+    b = C.c_void_p(C.addressof(buf))
+    f, d, i64 = C.c_float, C.c_double, C.c_int64
+    refusals = [
+        ("abi.hip", lambda: raw.texgs_preprocess_forward(None, None, None, None), b"frame is NULL"),
+        ("loss.hip", lambda: raw.texgs_geom_losses(None, None, None, None, None, None, 0, 8, f(0), f(0), f(1), f(0), b, None, None, None),
+         b"image size and gamma must be positive"),
+        ("uvnet.hip", lambda: raw.texgs_uv_pack(b, 99, b, None), b"precision must be TEXGS_UV_FP32, TEXGS_UV_BF16X3 or TEXGS_UV_MIXED"),
+        ("uvmap.hip", lambda: raw.texgs_hashgrid_forward(None, b, b, 4, b, None), b"grid is NULL"),
+        ("points.hip", lambda: raw.texgs_farthest_points(b, 0, 1, 0, b, b, None), b"n < 1"),
+        ("cubetex.hip", lambda: raw.texgs_cube_sample(b, 1, 3, b, 4, 0, 0, b, None), b"R < 2: a cubemap face needs at least 2 x 2 texels"),
+        ("density.hip", lambda: raw.texgs_density_stats(b, b, -1, b, b, b, None), b"n < 0"),
+        ("metrics.hip", lambda: raw.texgs_eval_metrics(b, b, None, None, None, 3, 8, 0, b, b, None),
+         b"H and W must be at least 7: the 7x7 SSIM window does not fit"),
+        ("selftest.hip", lambda: raw.texgs_selftest_waveops(None, None, None), b"NULL argument"),
+        ("optim.hip", lambda: raw.texgs_adam_step(None, -1, 0, None), b"count < 0"),
+        ("mlp.hip", lambda: raw.texgs_mlp_forward(None, b, b, 4, b, b, None), b"mlp is NULL"),
+        ("present.hip", lambda: raw.texgs_present(None, None), b"present descriptor is NULL"),
+        ("ingest.hip", lambda: raw.texgs_rgba_composite(b, b, 20000, 4, d(0), d(0), d(0), None),
+         b"20000 x 4: an image side above 16384 is not supported"),
+        ("surface.hip", lambda: raw.texgs_surface_compose(None, None), b"compose descriptor is NULL"),
+        ("lpips.hip", lambda: raw.texgs_conv3x3_pack(b, 0, 16, 0, b, None), b"Cin must be in [1,512], got 0"),
+        ("lpips_grad.hip", lambda: raw.texgs_lpips_gate(b, b, i64(0), None), b"n must be in [1,2^40), got 0"),
+        ("params.hip", lambda: raw.texgs_params_activate(None, None, C.c_size_t(0), None), b"activate descriptor is NULL"),
+        ("retexture.hip", lambda: raw.texgs_retexture_cross(None, None), b"retexture cross descriptor is NULL"),
+        ("shcolor.hip", lambda: raw.texgs_sh_colors_forward(None, None, 1, None), b"sh colours descriptor is NULL"),
+    ]
+    build = abi_check.build_script()
+    assert sorted(u for u, _, _ in refusals) == sorted(set(build.UNITS) - {"preprocess.hip", "binning.hip", "render.hip"})
+    assert len({text for _, _, text in refusals}) == len(refusals)
+    for unit, call, text in refusals + refusals[-2::-1]:
+        assert raw.texgs_last_error() != text, unit
+        assert call() != 0, unit
+        assert raw.texgs_last_error() == text, (unit, raw.texgs_last_error())
+
+
+def unit_of(header, name):
+    """The unit that defines an entry point: a stage's header names its unit; texgs.h is shared by the stages older than that rule"""
+    if header == "texgs_multiview.h":
+        return "abi.hip"
+    if header != "texgs.h":
+        return header[len("texgs_"):-len(".h")] + ".hip"
+    for unit, names in {"loss.hip": r"rgb_alpha_loss|geom_losses|norm_from_depth", "uvnet.hip": r"uv_\w+", "uvmap.hip": r"hashgrid_\w+|chamfer_nn\w*",
+                        "points.hip": r"knn3_\w+|fps_temp_bytes|farthest_points", "cubetex.hip": r"cube_\w+", "density.hip": r"density_\w+",
+                        "metrics.hip": r"eval_metrics\w*", "selftest.hip": r"selftest_waveops"}.items():
+        if re.fullmatch("texgs_(?:%s)" % names, name):
+            return unit
+    return "abi.hip"
+
+
+def test_each_prototype_is_defined_in_its_own_unit():
+    """Every function that a header of include/ declares is defined in exactly one file of csrc/: the unit of its stage, where its
+    launcher and its argument checks are; abi.hip has the rasterizer's (K1-K8, the batched front end, the SH flush)."""
+    csrc = os.path.join(ROOT, "texture-gs_amd", "csrc")
+    code = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc))}
+    headers = sorted(h for h in os.listdir(abi_check.INC) if h.endswith(".h"))
+    assert len(headers) == 12
+    seen = 0
+    for header in headers:
+        for name in abi_check.prototypes(os.path.join(abi_check.INC, header)):
+            definition = re.compile(r'^(?:extern "C" )?(?:const )?\w+\s*\*?\s*%s\s*\([^;{}]*\)\s*\{' % name, re.M)       # at the start of a line, with a body
+            assert [f for f, text in code.items() if definition.search(text)] == [unit_of(header, name)], (header, name)
+            seen += 1
+    assert seen == 88
+    assert unit_of("texgs.h", "texgs_mark_visible") == "abi.hip" and unit_of("texgs_present.h", "texgs_cube_cross") == "present.hip"

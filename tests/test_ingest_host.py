@@ -138,7 +138,7 @@ def test_header_is_plain_c99_and_stands_alone(tmp_path):
     text = open(HDR).read()
     assert sorted(re.findall(r"#include\s+[<\"]([^>\"]+)[>\"]", text)) == ["stddef.h", "stdint.h"]
     assert "TEXGS_ABI_VERSION" not in re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    assert '#include "texgs_ingest.h"' in open(os.path.join(ROOT, "texture-gs_amd", "csrc", "common.h")).read()
+    assert '#include "texgs_ingest.h"' in open(os.path.join(ROOT, "texture-gs_amd", "csrc", "ingest.hip")).read()
 
 
 def test_library_exports_the_entries_and_the_signatures_match_the_prototypes(lib_built):
@@ -153,8 +153,8 @@ def test_library_exports_the_entries_and_the_signatures_match_the_prototypes(lib
     assert lib is _lib.load() and lib.texgs_resize_u8.argtypes == ingest.SIGNATURES["texgs_resize_u8"][1]
     # its own table: neither the one tests/test_abi.py pins to texgs.h nor the output stage's
     assert not any(n in _lib.SIGNATURES or n in present.SIGNATURES for n in protos) and not hasattr(_lib, "ResizeStruct")
-    build = open(os.path.join(ROOT, "texture-gs_amd", "build.py")).read()
-    assert build.count("texgs_ingest.h") >= 2 and re.search(r'"ingest\.hip": \["-ffp-contract=off"\]', build)
+    build = abi_check.build_knows_header(HDR)
+    assert build.UNITS["ingest.hip"] == ["-ffp-contract=off"]
 
 
 def test_c_entries_refuse_bad_arguments_before_any_launch(lib_built):

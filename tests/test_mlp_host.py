@@ -106,7 +106,7 @@ def test_header_is_plain_c99_and_stands_alone(tmp_path):
     subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-pedantic", "-I", INC, "-c", str(src), "-o", str(tmp_path / "c.o")])
     text = open(HDR).read()
     assert sorted(re.findall(r"#include\s+[<\"]([^>\"]+)[>\"]", text)) == ["stddef.h", "stdint.h"]
-    assert '#include "texgs_mlp.h"' in open(os.path.join(ROOT, "texture-gs_amd", "csrc", "common.h")).read()
+    assert '#include "texgs_mlp.h"' in open(os.path.join(ROOT, "texture-gs_amd", "csrc", "mlp.hip")).read()
 
 
 def test_library_exports_the_entries_and_the_signatures_match_the_prototypes(lib_built):
@@ -122,8 +122,8 @@ def test_library_exports_the_entries_and_the_signatures_match_the_prototypes(lib
     # the mirror and the signatures live in texgs/mlp.py, not in the table that tests/test_abi.py pins to texgs.h
     assert not any(n in _lib.SIGNATURES for n in protos) and not hasattr(_lib, "MlpStruct")
     # the build knows the header: it is a dependency of every unit and part of the build id
-    build = open(os.path.join(ROOT, "texture-gs_amd", "build.py")).read()
-    assert build.count("texgs_mlp.h") >= 2 and '"mlp.hip"' in build
+    build = abi_check.build_knows_header(HDR)
+    assert "mlp.hip" in build.UNITS
 
 
 def test_param_count_and_the_c_refusals_need_no_gpu(lib_built):

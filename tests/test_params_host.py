@@ -243,7 +243,7 @@ def test_header_compiles_as_c_and_as_cpp_and_stands_alone(tmp_path):
     text = open(HDR).read()
     assert sorted(re.findall(r"#include\s+[<\"]([^>\"]+)[>\"]", text)) == ["stddef.h", "stdint.h"]
     assert "TEXGS_ABI_VERSION" not in re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    assert '#include "texgs_params.h"' in open(os.path.join(CSRC, "common.h")).read()
+    assert '#include "texgs_params.h"' in open(os.path.join(CSRC, "params.hip")).read()
     assert re.search(r"#define TEXGS_ABI_VERSION 19\b", open(os.path.join(INC, "texgs.h")).read())
     # the kernels: plain C++, no inline assembly
     for name in ("params.hip", "params_math.h"):
@@ -263,8 +263,8 @@ def test_library_exports_the_entries_and_the_signatures_match_the_prototypes(lib
     assert lib is _lib.load() and lib.texgs_params_activate.argtypes == params.SIGNATURES["texgs_params_activate"][1]
     assert lib.texgs_abi_version() == 19
     assert not any(n in _lib.SIGNATURES for n in protos) and not hasattr(_lib, "ParamsActivateStruct")
-    build = open(os.path.join(ROOT, "texture-gs_amd", "build.py")).read()
-    assert build.count("texgs_params.h") >= 2 and re.search(r'"params\.hip": \["-ffp-contract=off"\]', build)
+    build = abi_check.build_knows_header(HDR)
+    assert build.UNITS["params.hip"] == ["-ffp-contract=off"]
 
 
 def test_c_entries_refuse_bad_arguments_before_any_launch(lib_built):

@@ -127,7 +127,7 @@ def test_header_is_plain_c99_and_stands_alone(tmp_path):
     text = open(HDR).read()
     assert sorted(re.findall(r"#include\s+[<\"]([^>\"]+)[>\"]", text)) == ["stddef.h", "stdint.h"]
     assert "TEXGS_ABI_VERSION" not in re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    assert '#include "texgs_present.h"' in open(os.path.join(ROOT, "texture-gs_amd", "csrc", "common.h")).read()
+    assert '#include "texgs_present.h"' in open(os.path.join(ROOT, "texture-gs_amd", "csrc", "present.hip")).read()
 
 
 def test_library_exports_the_entries_and_the_signatures_match_the_prototypes(lib_built):
@@ -143,8 +143,8 @@ def test_library_exports_the_entries_and_the_signatures_match_the_prototypes(lib
     # the mirrors and the signatures live in texgs/present.py, not in the table that tests/test_abi.py pins to texgs.h
     assert not any(n in _lib.SIGNATURES for n in protos) and not hasattr(_lib, "PresentStruct")
     # the build knows the unit: its flag, the header as a dependency of every unit and as part of the build id
-    build = open(os.path.join(ROOT, "texture-gs_amd", "build.py")).read()
-    assert build.count("texgs_present.h") >= 2 and re.search(r'"present\.hip": \["-ffp-contract=off"\]', build)
+    build = abi_check.build_knows_header(HDR)
+    assert build.UNITS["present.hip"] == ["-ffp-contract=off"]
 
 
 def test_c_entries_refuse_bad_arguments_before_any_launch(lib_built):

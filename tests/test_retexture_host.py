@@ -184,13 +184,13 @@ def test_header_compiles_as_c_and_as_cpp_and_stands_alone(tmp_path):
     text = open(HDR).read()
     assert sorted(re.findall(r"#include\s+[<\"]([^>\"]+)[>\"]", text)) == ["stddef.h", "stdint.h"]
     assert "TEXGS_ABI_VERSION" not in re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    assert '#include "texgs_retexture.h"' in open(os.path.join(CSRC, "common.h")).read()
+    assert '#include "texgs_retexture.h"' in open(os.path.join(CSRC, "retexture.hip")).read()
     assert re.search(r"#define TEXGS_ABI_VERSION 19\b", open(os.path.join(INC, "texgs.h")).read())
     for name in ("retexture.hip", "retexture_math.h"):         # the kernels: plain C++, no inline assembly, no atomics, no LDS
         code = open(os.path.join(CSRC, name)).read()
         assert not re.search(r"\basm\b|__asm|atomic[A-Z_a-z]*\(|__shared__", code), name
-    build = open(os.path.join(ROOT, "texture-gs_amd", "build.py")).read()
-    assert build.count("texgs_retexture.h") >= 2 and re.search(r'"retexture\.hip": \["-ffp-contract=off"\]', build)
+    build = abi_check.build_knows_header(HDR)
+    assert build.UNITS["retexture.hip"] == ["-ffp-contract=off"]
 
 
 def test_structs_match_c_layout(tmp_path):

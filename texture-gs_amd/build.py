@@ -1,6 +1,8 @@
 """Build libtexgs.so (hipcc, gfx950 only) in-tree.  Usage: python texture-gs_amd/build.py [--force] [--verbose]
 
-Objects are rebuilt only when their sources are newer.  preprocess.hip is built with -ffp-contract=off (its
+One object per unit of UNITS; a stage is one unit (its kernels, launchers, argument checks and C entry points) plus its
+header in include/.  An object is rebuilt when its unit or any header of HEADERS is newer; HEADERS is every *.h under
+include/ and csrc/, and build_id() hashes the same list.  preprocess.hip is built with -ffp-contract=off (its
 fp32 operation order is part of the bit-exact key/rect/radius contract) and so is points.hip (its squared distance is
 compared bit for bit), density.hip (its per-step statistics likewise), optim.hip (the Adam step's arithmetic likewise) and
 metrics.hip (its fp64 sums are compared with numpy's), present.hip (its output bytes and floats are compared bit for bit) and
@@ -53,27 +55,17 @@ UNITS = {
     "shcolor.hip": ["-ffp-contract=off"],     # the SH evaluation in the reference's operation order is a bit-exact contract: one rounding per operation
     "abi.hip": [],
 }
-HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "wave_ops.h"), os.path.join(CSRC, "render_bwd_body.h"),
-           os.path.join(ROOT, "include", "texgs.h"), os.path.join(ROOT, "include", "texgs_optim.h"),
-           os.path.join(ROOT, "include", "texgs_multiview.h"), os.path.join(ROOT, "include", "texgs_mlp.h"),
-           os.path.join(ROOT, "include", "texgs_present.h"), os.path.join(ROOT, "include", "texgs_ingest.h"),
-           os.path.join(ROOT, "include", "texgs_surface.h"), os.path.join(ROOT, "include", "texgs_lpips.h"),
-           os.path.join(ROOT, "include", "texgs_lpips_grad.h"), os.path.join(ROOT, "include", "texgs_params.h"),
-           os.path.join(CSRC, "params_math.h"), os.path.join(ROOT, "include", "texgs_retexture.h"),
-           os.path.join(CSRC, "retexture_math.h"), os.path.join(ROOT, "include", "texgs_shcolor.h"),
-           os.path.join(CSRC, "shcolor_math.h"), os.path.join(CSRC, "texrec_math.h")]
+# every header a unit can include; the one list that both the rebuild rule (build) and build_id() read
+HEADERS = sorted(os.path.join(d, f) for d in (os.path.join(ROOT, "include"), CSRC) for f in os.listdir(d) if f.endswith(".h"))
 
 
 def build_id():
-    """Identity of what libtexgs.so is built FROM: sha256 over csrc/*, the headers of include/ and the compile flags (16 hex digits).
+    """Identity of what libtexgs.so is built FROM: sha256 over the units of UNITS, HEADERS and the compile flags (16 hex digits).
     build() bakes it into the library (texgs_build_id()); texgs/_lib.py recomputes it from the tree and refuses a library that
     was built from other sources -- the prebuilt .so is what travels to the GPU box, mtimes do not."""
     import hashlib
     h = hashlib.sha256()
-    files = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))) \
-        + [os.path.join(ROOT, "include", f) for f in ("texgs.h", "texgs_optim.h", "texgs_multiview.h", "texgs_mlp.h", "texgs_present.h", "texgs_ingest.h",
-                                                         "texgs_surface.h", "texgs_lpips.h", "texgs_lpips_grad.h", "texgs_params.h", "texgs_retexture.h", "texgs_shcolor.h")]
-    for f in files:
+    for f in sorted(os.path.join(CSRC, u) for u in UNITS) + HEADERS:
         h.update(os.path.basename(f).encode())
         h.update(open(f, "rb").read())
     h.update(repr((COMMON[:4], sorted(UNITS.items()), os.environ.get("TEXGS_EXTRA_FLAGS", ""))).encode())

@@ -14,6 +14,7 @@
 // and e.g. leaving +x over s > 1 makes -z dominant, where s' = -x/|z| -> -1 (its column 0, edge 0) and t' = -y = t (same row, not
 // reversed): entry (+x, edge 1) = (-z, edge 0, same).  The other 23 follow the same way.
 #include "common.h"
+#include "abi_support.h"
 
 #define CT_BLOCK 256
 
@@ -228,29 +229,78 @@ __global__ __launch_bounds__(CT_BLOCK) void k_cube_nearest_bwd(int R, int C, con
 
 static inline uint32_t ct_blocks(long long n) { return (uint32_t)((n + CT_BLOCK - 1) / CT_BLOCK); }
 
-hipError_t launch_cube_sample(const float* tex, int R, int C, const float* dirs, int N, int filter, int tap_map, float* out, hipStream_t s) {
+static hipError_t launch_cube_sample(const float* tex, int R, int C, const float* dirs, int N, int filter, int tap_map, float* out, hipStream_t s) {
     if (N == 0) return hipSuccess;
     if (tap_map) hipLaunchKernelGGL(k_cube_sample<true>, dim3(ct_blocks(N)), dim3(CT_BLOCK), 0, s, tex, R, C, dirs, N, filter, out);
     else         hipLaunchKernelGGL(k_cube_sample<false>, dim3(ct_blocks(N)), dim3(CT_BLOCK), 0, s, tex, R, C, dirs, N, filter, out);
     return hipGetLastError();
 }
 
-hipError_t launch_cube_latlong(const float* tex, int R, int C, int H, int W, int tap_map, float* out, hipStream_t s) {
+static hipError_t launch_cube_latlong(const float* tex, int R, int C, int H, int W, int tap_map, float* out, hipStream_t s) {
     const uint32_t nb = ct_blocks((long long)H * W);
     if (tap_map) hipLaunchKernelGGL(k_cube_latlong<true>, dim3(nb), dim3(CT_BLOCK), 0, s, tex, R, C, H, W, out);
     else         hipLaunchKernelGGL(k_cube_latlong<false>, dim3(nb), dim3(CT_BLOCK), 0, s, tex, R, C, H, W, out);
     return hipGetLastError();
 }
 
-hipError_t launch_cube_sample_backward(const float* tex, int R, int C, const float* dirs, int N, const float* g_out, float* d_tex,
+static hipError_t launch_cube_sample_backward(const float* tex, int R, int C, const float* dirs, int N, const float* g_out, float* d_tex,
                                 float* d_dirs, hipStream_t s) {
     if (N == 0) return hipSuccess;
     hipLaunchKernelGGL(k_cube_sample_bwd, dim3(ct_blocks(N)), dim3(CT_BLOCK), 0, s, tex, R, C, dirs, N, g_out, d_tex, d_dirs);
     return hipGetLastError();
 }
 
-hipError_t launch_cube_sample_nearest_backward(int R, int C, const float* dirs, int N, const float* g_out, float* d_tex, hipStream_t s) {
+static hipError_t launch_cube_sample_nearest_backward(int R, int C, const float* dirs, int N, const float* g_out, float* d_tex, hipStream_t s) {
     if (N == 0) return hipSuccess;
     hipLaunchKernelGGL(k_cube_nearest_bwd, dim3(ct_blocks(N)), dim3(CT_BLOCK), 0, s, R, C, dirs, N, g_out, d_tex);
     return hipGetLastError();
 }
+
+extern "C" {
+
+static int cube_shape_ok(int32_t R, int32_t C) {
+    if (R < 2) return fail_msg("R < 2: a cubemap face needs at least 2 x 2 texels");
+    if (C < 1) return fail_msg("C < 1");
+    if (6ll * R * R * C >= (1ll << 31)) return fail_msg("6 R R C must be below 2^31");
+    return 0;
+}
+
+int texgs_cube_sample(const float* tex, int32_t R, int32_t C, const float* dirs, int32_t N, int32_t filter, int32_t tap_map,
+                      float* out, void* stream) {
+    if (int r = cube_shape_ok(R, C)) return r;
+    if (N < 0) return fail_msg("N < 0");
+    if (filter != TEXGS_CUBE_LINEAR && filter != TEXGS_CUBE_NEAREST) return fail_msg("filter must be TEXGS_CUBE_LINEAR or TEXGS_CUBE_NEAREST");
+    if (!tex || (N > 0 && (!dirs || !out))) return fail_msg("NULL argument");
+    hipStream_t s = (hipStream_t)stream;
+    return launched("cube_sample", launch_cube_sample(tex, R, C, dirs, N, filter, tap_map, out, s), s, false);
+}
+
+int texgs_cube_latlong(const float* tex, int32_t R, int32_t C, int32_t H, int32_t W, int32_t tap_map, float* out, void* stream) {
+    if (int r = cube_shape_ok(R, C)) return r;
+    if (H < 1 || W < 1) return fail_msg("H and W must be positive");
+    if ((long long)H * W >= (1ll << 31)) return fail_msg("H W must be below 2^31");
+    if (!tex || !out) return fail_msg("NULL argument");
+    hipStream_t s = (hipStream_t)stream;
+    return launched("cube_latlong", launch_cube_latlong(tex, R, C, H, W, tap_map, out, s), s, false);
+}
+
+int texgs_cube_sample_backward(const float* tex, int32_t R, int32_t C, const float* dirs, int32_t N, const float* g_out,
+                               float* d_tex, float* d_dirs, void* stream) {
+    if (int r = cube_shape_ok(R, C)) return r;
+    if (N < 0) return fail_msg("N < 0");
+    if (!d_tex && !d_dirs) return fail_msg("d_tex and d_dirs are both NULL: nothing to compute");
+    if ((d_dirs && !tex) || (N > 0 && (!dirs || !g_out))) return fail_msg("NULL argument");
+    hipStream_t s = (hipStream_t)stream;
+    return launched("cube_sample_backward", launch_cube_sample_backward(tex, R, C, dirs, N, g_out, d_tex, d_dirs, s), s, false);
+}
+
+int texgs_cube_sample_nearest_backward(int32_t R, int32_t C, const float* dirs, int32_t N, const float* g_out, float* d_tex,
+                                       void* stream) {
+    if (int r = cube_shape_ok(R, C)) return r;
+    if (N < 0) return fail_msg("N < 0");
+    if (!d_tex || (N > 0 && (!dirs || !g_out))) return fail_msg("NULL argument");
+    hipStream_t s = (hipStream_t)stream;
+    return launched("cube_sample_nearest_backward", launch_cube_sample_nearest_backward(R, C, dirs, N, g_out, d_tex, s), s, false);
+}
+
+}  // extern "C"

@@ -3,6 +3,7 @@
 // compared bit for bit (sqrtf and '/' are the correctly rounded ones here; __fsqrt_rn is NOT: this toolchain maps it to the native
 // approximation).  No global atomics and no workgroup waits on another: the scan is three plain launches.
 #include "common.h"
+#include "abi_support.h"
 
 namespace {
 
@@ -254,19 +255,19 @@ inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 }  // namespace
 
-hipError_t launch_density_stats(const float* grad, const int32_t* radii, int n, float* accum, float* denom, float* max_radii, hipStream_t s) {
+static hipError_t launch_density_stats(const float* grad, const int32_t* radii, int n, float* accum, float* denom, float* max_radii, hipStream_t s) {
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(k_density_stats, dim3(((uint32_t)n + DN_BLOCK - 1) / DN_BLOCK), dim3(DN_BLOCK), 0, s, grad, radii, (uint32_t)n, accum,
                        denom, max_radii);
     return hipGetLastError();
 }
 
-size_t density_plan_temp_bytes(int n) {
+static size_t density_plan_temp_bytes(int n) {
     const size_t tiles = ((size_t)(n > 0 ? n : 1) + DN_TILE - 1) / DN_TILE;
     return align256(tiles * DN_CH * sizeof(uint32_t));
 }
 
-hipError_t launch_density_plan(const TexGSDensityPlan* p, uint8_t* action, int32_t* rank, uint32_t* totals, void* temp, hipStream_t s) {
+static hipError_t launch_density_plan(const TexGSDensityPlan* p, uint8_t* action, int32_t* rank, uint32_t* totals, void* temp, hipStream_t s) {
     const uint32_t n = (uint32_t)p->n;
     if (n == 0) return hipMemsetAsync(totals, 0, DN_CH * sizeof(uint32_t), s);
     const uint32_t tiles = (n + DN_TILE - 1) / DN_TILE;
@@ -281,7 +282,7 @@ hipError_t launch_density_plan(const TexGSDensityPlan* p, uint8_t* action, int32
     return hipGetLastError();
 }
 
-hipError_t launch_density_move(const TexGSDensityMove* m, hipStream_t s) {
+static hipError_t launch_density_move(const TexGSDensityMove* m, hipStream_t s) {
     MoveArgs a;
     unsigned long long blocks = 0;
     for (int d = 0; d < m->rows; ++d) {
@@ -299,3 +300,48 @@ hipError_t launch_density_move(const TexGSDensityMove* m, hipStream_t s) {
     hipLaunchKernelGGL(k_density_move, dim3((uint32_t)blocks), dim3(DN_BLOCK), 0, s, a);
     return hipGetLastError();
 }
+
+extern "C" {
+
+int texgs_density_stats(const float* grad, const int32_t* radii, int32_t n, float* accum, float* denom, float* max_radii, void* stream) {
+    if (n < 0) return fail_msg("n < 0");
+    if (n > 0 && (!grad || !radii || !accum || !denom || !max_radii)) return fail_msg("NULL argument");
+    hipStream_t s = (hipStream_t)stream;
+    return launched("density_stats", launch_density_stats(grad, radii, n, accum, denom, max_radii, s), s, false);
+}
+
+size_t texgs_density_plan_temp_bytes(int32_t n) { return density_plan_temp_bytes(n); }
+
+int texgs_density_plan(const TexGSDensityPlan* plan, uint8_t* action, int32_t* rank, uint32_t* totals, void* temp, void* stream) {
+    if (!plan || !totals) return fail_msg("NULL argument");
+    if (plan->n < 0) return fail_msg("n < 0");
+    if (plan->n > 0 && (!plan->scaling || !plan->opacity || !action || !rank || !temp)) return fail_msg("NULL argument");
+    if (plan->n > 0 && plan->densify && (!plan->accum || !plan->denom)) return fail_msg("accum and denom are required to densify");
+    if (plan->densify && !(plan->max_grad > 0.0f)) return fail_msg("max_grad must be positive (with 0 the reference splits its own clones)");
+    hipStream_t s = (hipStream_t)stream;
+    return launched("density_plan", launch_density_plan(plan, action, rank, totals, temp, s), s, false);
+}
+
+int texgs_density_move(const TexGSDensityMove* m, void* stream) {
+    if (!m) return fail_msg("NULL argument");
+    if (m->n < 0 || m->n_kept < 0 || m->n_clone < 0 || m->n_split < 0 || m->n_child < 0) return fail_msg("negative count");
+    if (m->n_kept > m->n || m->n_clone > m->n || m->n_split > m->n || m->n_child > m->n_split) return fail_msg("totals exceed n");
+    if ((int64_t)m->n_kept + m->n_clone + 2ll * m->n_child >= (1ll << 31)) return fail_msg("the new row count reaches 2^31");
+    if (m->rows < 0 || m->rows > TEXGS_DENSITY_MAX_ROWS) return fail_msg("rows must be in [0, TEXGS_DENSITY_MAX_ROWS]");
+    if (m->n == 0 || m->rows == 0) return 0;
+    if (!m->action || !m->rank) return fail_msg("NULL argument");
+    const bool out_rows = m->n_kept + m->n_clone + m->n_child > 0;
+    for (int d = 0; d < m->rows; ++d) {
+        const TexGSDensityRow& r = m->row[d];
+        if (r.width < 1) return fail_msg("row width < 1");
+        if (r.kind < TEXGS_DENSITY_ROW_COPY || r.kind > TEXGS_DENSITY_ROW_XYZ) return fail_msg("unknown row kind");
+        if (r.kind == TEXGS_DENSITY_ROW_XYZ && r.width != 3) return fail_msg("an XYZ row has width 3");
+        if (!r.src || (out_rows && !r.dst)) return fail_msg("NULL row pointer");
+        if (r.kind == TEXGS_DENSITY_ROW_XYZ && m->n_child > 0 && (!m->scaling || !m->rotation || !m->noise))
+            return fail_msg("an XYZ row with children needs scaling, rotation and noise");
+    }
+    if (!out_rows) return 0;        // everything pruned: there is no row to write
+    return launched("density_move", launch_density_move(m, (hipStream_t)stream), (hipStream_t)stream, false);
+}
+
+}  // extern "C"

@@ -14,6 +14,8 @@
 // Only the LAST dword of a caller's buffer is read bytewise when the buffer ends inside it (`ld_dword`), so nothing is read past an
 // end.  The intermediate between the passes lives in `temp` with its rows padded to whole dwords and indexed by SOURCE row.
 #include "common.h"
+#include "abi_support.h"
+#include "texgs_ingest.h"
 
 #include <math.h>
 
@@ -445,17 +447,17 @@ Plan make_plan(int H, int W, int C, int h, int w, int filter) {
 
 }  // namespace
 
-// (the arguments of everything below were validated by abi.hip)
-int ingest_ksize(int inS, int outS, int filter) { return make_axis(inS, outS, filter).ksize; }
+// (the arguments of these are validated by the entry points below)
+static int ingest_ksize(int inS, int outS, int filter) { return make_axis(inS, outS, filter).ksize; }
 
-hipError_t launch_resize_taps(int inS, int outS, int filter, int32_t* taps, int32_t* bounds, hipStream_t s) {
+static hipError_t launch_resize_taps(int inS, int outS, int filter, int32_t* taps, int32_t* bounds, hipStream_t s) {
     hipLaunchKernelGGL(k_taps, dim3((outS + IB - 1) / IB), dim3(IB), 0, s, inS, outS, filter, taps, bounds);
     return hipGetLastError();
 }
 
-size_t resize_temp_bytes(int H, int W, int C, int h, int w, int filter) { return make_plan(H, W, C, h, w, filter).total; }
+static size_t resize_temp_bytes(int H, int W, int C, int h, int w, int filter) { return make_plan(H, W, C, h, w, filter).total; }
 
-hipError_t launch_resize_u8(const TexGSResize* r, void* temp, hipStream_t s) {
+static hipError_t launch_resize_u8(const TexGSResize* r, void* temp, hipStream_t s) {
     const int H = r->src_height, W = r->src_width, C = r->channels, h = r->height, w = r->width;
     const Plan p = make_plan(H, W, C, h, w, r->filter);
     uint8_t* t = (uint8_t*)temp;
@@ -519,8 +521,86 @@ hipError_t launch_resize_u8(const TexGSResize* r, void* temp, hipStream_t s) {
     return hipGetLastError();
 }
 
-hipError_t launch_rgba_composite(const uint8_t* rgba, uint8_t* out, int H, int W, double bg0, double bg1, double bg2, hipStream_t s) {
+static hipError_t launch_rgba_composite(const uint8_t* rgba, uint8_t* out, int H, int W, double bg0, double bg1, double bg2, hipStream_t s) {
     const uint32_t P = (uint32_t)H * (uint32_t)W;
     hipLaunchKernelGGL(k_composite, dim3(quad_grid(P)), dim3(IB), 0, s, (const uint32_t*)rgba, out, P, bg0, bg1, bg2);
     return hipGetLastError();
 }
+
+extern "C" {
+
+// include/texgs_ingest.h: every argument is checked before the first launch, so a refused call has changed nothing
+// One axis in_size -> out_size: its ksize, or 0 with the cause in the error text
+static int check_resize_axis(const char* what, int32_t in_size, int32_t out_size, int32_t filter) {
+    if (filter != TEXGS_INGEST_BICUBIC && filter != TEXGS_INGEST_BILINEAR && filter != TEXGS_INGEST_BOX) {
+        failf("unknown filter %lld (TEXGS_INGEST_BICUBIC, _BILINEAR or _BOX)", (long long)filter);
+        return 0;
+    }
+    if (in_size < 1 || out_size < 1) {
+        failf("%s: sizes must be positive, got %d -> %d", what, in_size, out_size);
+        return 0;
+    }
+    if (in_size > TEXGS_INGEST_MAX_SIDE || out_size > TEXGS_INGEST_MAX_SIDE) {
+        failf("%s: %d -> %d: an image side above %d is not supported", what, in_size, out_size, TEXGS_INGEST_MAX_SIDE);
+        return 0;
+    }
+    const int k = ingest_ksize(in_size, out_size, filter);
+    if (k > TEXGS_INGEST_MAX_KSIZE) {
+        failf("%s: %d -> %d needs ksize %d taps per output, above the limit of %d", what, in_size, out_size, k,
+              TEXGS_INGEST_MAX_KSIZE);
+        return 0;
+    }
+    return k;
+}
+
+static int check_resize_shape(int32_t H, int32_t W, int32_t C, int32_t h, int32_t w, int32_t filter) {
+    if (C == 4) return fail_msg("channels = 4 (RGBA) is not supported: Pillow premultiplies alpha before it resamples; composite first");
+    if (C != 1 && C != 3) return failf("channels must be 1 or 3, got %lld", (long long)C);
+    if (!check_resize_axis("width", W, w, filter) || !check_resize_axis("height", H, h, filter)) return -1;
+    return 0;
+}
+
+int32_t texgs_resize_ksize(int32_t in_size, int32_t out_size, int32_t filter) { return check_resize_axis("axis", in_size, out_size, filter); }
+
+int texgs_resize_taps(int32_t in_size, int32_t out_size, int32_t filter, int32_t* taps, int32_t* bounds, void* stream) {
+    if (!check_resize_axis("axis", in_size, out_size, filter)) return -1;
+    if (!taps || !bounds) return fail_msg("NULL argument (taps or bounds)");
+    if (((uintptr_t)taps | (uintptr_t)bounds) & 3) return fail_msg("taps and bounds must be 4-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    return launched("resize_taps", launch_resize_taps(in_size, out_size, filter, taps, bounds, s), s, false);
+}
+
+size_t texgs_resize_temp_bytes(int32_t src_height, int32_t src_width, int32_t channels, int32_t height, int32_t width, int32_t filter) {
+    return check_resize_shape(src_height, src_width, channels, height, width, filter)
+               ? 0 : resize_temp_bytes(src_height, src_width, channels, height, width, filter);
+}
+
+int texgs_resize_u8(const TexGSResize* r, void* temp, size_t temp_bytes, void* stream) {
+    if (!r) return fail_msg("resize descriptor is NULL");
+    if (int e = check_resize_shape(r->src_height, r->src_width, r->channels, r->height, r->width, r->filter)) return e;
+    if (!r->src || !temp) return fail_msg("NULL argument (src or temp)");
+    if (r->flags & ~TEXGS_INGEST_SIGNED) return fail_msg("unknown bit in flags");
+    if (!r->out_u8 && !r->out_chw && !r->out_mask) return fail_msg("no output requested (out_u8, out_chw and out_mask are all NULL)");
+    if (r->mul && !r->out_chw) return fail_msg("mul is read with out_chw only");
+    if (((uintptr_t)r->src | (uintptr_t)r->mul | (uintptr_t)r->out_u8 | (uintptr_t)r->out_chw | (uintptr_t)r->out_mask | (uintptr_t)temp) & 3)
+        return fail_msg("src, mul, out_u8, out_chw, out_mask and temp must be 4-byte aligned");
+    if (temp_bytes < resize_temp_bytes(r->src_height, r->src_width, r->channels, r->height, r->width, r->filter))
+        return fail_msg("temp is smaller than texgs_resize_temp_bytes");
+    hipStream_t s = (hipStream_t)stream;
+    return launched("resize_u8", launch_resize_u8(r, temp, s), s, false);
+}
+
+int texgs_rgba_composite(const uint8_t* rgba, uint8_t* out, int32_t height, int32_t width, double bg_r, double bg_g, double bg_b,
+                         void* stream) {
+    if (height < 1 || width < 1) return fail_msg("height and width must be positive");
+    if (height > TEXGS_INGEST_MAX_SIDE || width > TEXGS_INGEST_MAX_SIDE)
+        return failf("%lld x %lld: an image side above 16384 is not supported", (long long)height, (long long)width);
+    if (!rgba || !out) return fail_msg("NULL argument (rgba or out)");
+    if (((uintptr_t)rgba | (uintptr_t)out) & 3) return fail_msg("rgba and out must be 4-byte aligned");
+    if (!(bg_r >= 0.0 && bg_r <= 1.0 && bg_g >= 0.0 && bg_g <= 1.0 && bg_b >= 0.0 && bg_b <= 1.0))
+        return fail_msg("the background must lie in [0, 1]");
+    hipStream_t s = (hipStream_t)stream;
+    return launched("rgba_composite", launch_rgba_composite(rgba, out, height, width, bg_r, bg_g, bg_b, s), s, false);
+}
+
+}  // extern "C"

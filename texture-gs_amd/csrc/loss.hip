@@ -7,6 +7,7 @@
 //   k_ssim_bwd   the same (symmetric) window applied to the 3 partial maps -> dL/dI; + the L1 sign terms
 // The reference does this with 5 depthwise conv2d calls + ~25 elementwise kernels and their autograd.
 #include "common.h"
+#include "abi_support.h"
 
 namespace {
 
@@ -313,7 +314,7 @@ k_norm_from_depth(DepthNormArgs a, const float* __restrict__ viewmatrix, const f
 
 }  // namespace
 
-hipError_t launch_geom_losses(const float* norm, const float* gt_norm, const float* gt_image, const float* mask, const float* depth,
+static hipError_t launch_geom_losses(const float* norm, const float* gt_norm, const float* gt_image, const float* mask, const float* depth,
                        const float* gt_depth, int H, int W, float lambda_norm, float lambda_smooth, float gamma,
                        float lambda_depth, float* sums, float* d_norm, float* d_depth, hipStream_t s) {
     GeomArgs a;
@@ -331,7 +332,7 @@ hipError_t launch_geom_losses(const float* norm, const float* gt_norm, const flo
 }
 
 // sums[0..2] = sum|I-Igt|, sum SSIM, sum|A-Agt| (device); dL/dI and dL/dA are for d(loss) = 1
-hipError_t launch_rgb_alpha_loss(const float* image, const float* gt_image, const float* alpha, const float* gt_alpha, int H,
+static hipError_t launch_rgb_alpha_loss(const float* image, const float* gt_image, const float* alpha, const float* gt_alpha, int H,
                           int W, float lambda_dssim, float lambda_alpha, float* scratch, float* sums, float* d_image,
                           float* d_alpha, hipStream_t s) {
     Win win;
@@ -356,7 +357,7 @@ hipError_t launch_rgb_alpha_loss(const float* image, const float* gt_image, cons
     return st.after_launches();
 }
 
-hipError_t launch_norm_from_depth(const float* depth, const float* viewmatrix, float tanfovx, float tanfovy, int H, int W, float threshold,
+static hipError_t launch_norm_from_depth(const float* depth, const float* viewmatrix, float tanfovx, float tanfovy, int H, int W, float threshold,
                            float* out_norm, float* out_mask, hipStream_t s) {
     DepthNormArgs a;
     a.H = H; a.W = W; a.tx = tanfovx; a.ty = tanfovy; a.thr = threshold;
@@ -365,3 +366,39 @@ hipError_t launch_norm_from_depth(const float* depth, const float* viewmatrix, f
     hipLaunchKernelGGL(k_norm_from_depth, dim3((P + 255) / 256), dim3(256), 0, s, a, viewmatrix, depth, out_norm, out_mask);
     return hipGetLastError();
 }
+
+extern "C" {
+
+int texgs_rgb_alpha_loss(const float* image, const float* gt_image, const float* alpha, const float* gt_alpha,
+                         int32_t H, int32_t W, float lambda_dssim, float lambda_alpha, float* scratch, float* sums,
+                         float* dL_dimage, float* dL_dalpha, void* stream) {
+    if (!image || !gt_image || !scratch || !sums || !dL_dimage) return fail_msg("NULL argument");
+    if (H <= 0 || W <= 0) return fail_msg("image size must be positive");
+    hipStream_t s = (hipStream_t)stream;
+    return launched("rgb_alpha_loss", launch_rgb_alpha_loss(image, gt_image, alpha, gt_alpha, H, W, lambda_dssim, lambda_alpha, scratch,
+                                                            sums, dL_dimage, dL_dalpha, s), s, false);
+}
+
+int texgs_geom_losses(const float* norm, const float* gt_norm, const float* gt_image, const float* mask, const float* depth,
+                      const float* gt_depth, int32_t H, int32_t W, float lambda_norm, float lambda_smooth, float gamma,
+                      float lambda_depth, float* sums, float* dL_dnorm, float* dL_ddepth, void* stream) {
+    if (!sums) return fail_msg("NULL argument");
+    if (H <= 0 || W <= 0 || !(gamma > 0.f)) return fail_msg("image size and gamma must be positive");
+    if (lambda_norm != 0.f && (!norm || !gt_norm || !dL_dnorm)) return fail_msg("norm term needs norm, gt_norm, dL_dnorm");
+    if (lambda_smooth != 0.f && (!norm || !gt_image || !dL_dnorm)) return fail_msg("smoothness term needs norm, gt_image, dL_dnorm");
+    if (lambda_depth != 0.f && (!depth || !gt_depth || !dL_ddepth)) return fail_msg("depth term needs depth, gt_depth, dL_ddepth");
+    hipStream_t s = (hipStream_t)stream;
+    return launched("geom_losses", launch_geom_losses(norm, gt_norm, gt_image, mask, depth, gt_depth, H, W, lambda_norm, lambda_smooth,
+                                                      gamma, lambda_depth, sums, dL_dnorm, dL_ddepth, s), s, false);
+}
+
+int texgs_norm_from_depth(const float* depth, const float* viewmatrix, float tanfovx, float tanfovy, int32_t H, int32_t W,
+                          float threshold, float* out_norm, float* out_mask, void* stream) {
+    if (!depth || !viewmatrix || !out_norm || !out_mask) return fail_msg("NULL argument");
+    if (H <= 0 || W <= 0) return fail_msg("image size must be positive");
+    hipStream_t s = (hipStream_t)stream;
+    return launched("norm_from_depth", launch_norm_from_depth(depth, viewmatrix, tanfovx, tanfovy, H, W, threshold, out_norm, out_mask, s),
+                    s, false);
+}
+
+}  // extern "C"

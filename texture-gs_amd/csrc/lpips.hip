@@ -18,12 +18,14 @@
 //   800x800 pair.  Four instantiations: pool_in x affine.
 //   A tile never spans two images and nothing depends on the batch size: an image's output is the same bits in any slot.
 //   x and y are addressed through row / channel-plane / image strides (texgs_lpips.h; the dense ones when the descriptor's are 0).
-//   The grid is (pixel tiles of an image, cout tiles, B): abi.hip refuses 2^24 tiles or more, the launch's limit for x.
+//   The grid is (pixel tiles of an image, cout tiles, B): texgs_conv3x3 refuses 2^24 tiles or more, the launch's limit for x.
 // HEAD  k_lpips_head / k_lpips_head_reduce: one thread per pixel walks the channels twice (norms, then the weighted squared
 //   difference of the unit vectors) in f32 with one rounding per operation (build.py: -ffp-contract=off, so (a - b)^2 == (b - a)^2
 //   and swapping the images changes no bit); the pixel sums are f64: per thread, per block (a tree in LDS), then one block per
 //   pair adds the partials in a fixed order.  No atomics.
 #include "common.h"
+#include "lpips_checks.h"
+#include "texgs_lpips.h"
 
 namespace {
 
@@ -269,16 +271,16 @@ int lp_head_blocks(int h, int w) {
 
 }  // namespace
 
-size_t conv3x3_packed_bytes(int Cin, int Cout) { return (size_t)cv_cout_tiles(Cout) * cv_chunks(Cin) * CV_A_CHUNK * sizeof(float); }
+static size_t conv3x3_packed_bytes(int Cin, int Cout) { return (size_t)cv_cout_tiles(Cout) * cv_chunks(Cin) * CV_A_CHUNK * sizeof(float); }
 
-hipError_t launch_conv3x3_pack(const float* w, int Cin, int Cout, void* packed, hipStream_t s) {
+static hipError_t launch_conv3x3_pack(const float* w, int Cin, int Cout, void* packed, hipStream_t s) {
     const int total = (int)(conv3x3_packed_bytes(Cin, Cout) / sizeof(float));           // <= 512 * 512 * 9
     hipLaunchKernelGGL(k_conv3x3_pack, dim3((total + 255) / 256), dim3(256), 0, s, w, Cin, Cout, cv_chunks(Cin), total,
                        reinterpret_cast<float*>(packed));
     return hipGetLastError();
 }
 
-hipError_t launch_conv3x3(const TexGSConv3x3* d, hipStream_t s) {
+static hipError_t launch_conv3x3(const TexGSConv3x3* d, hipStream_t s) {
     const int Ho = d->pool_in ? d->H / 2 : d->H, Wo = d->pool_in ? d->W / 2 : d->W;
     const int tiles_x = (Wo + CV_TW - 1) / CV_TW, tiles_y = (Ho + CV_TH - 1) / CV_TH;
     const bool xd = !d->x_row && !d->x_chan && !d->x_img, yd = !d->y_row && !d->y_chan && !d->y_img;       // dense
@@ -298,9 +300,9 @@ hipError_t launch_conv3x3(const TexGSConv3x3* d, hipStream_t s) {
     return hipGetLastError();
 }
 
-size_t lpips_head_temp_bytes(int P, int h, int w) { return (size_t)P * lp_head_blocks(h, w) * sizeof(double); }
+static size_t lpips_head_temp_bytes(int P, int h, int w) { return (size_t)P * lp_head_blocks(h, w) * sizeof(double); }
 
-hipError_t launch_lpips_head(const TexGSLpipsHead* d, hipStream_t s) {
+static hipError_t launch_lpips_head(const TexGSLpipsHead* d, hipStream_t s) {
     const int nb = lp_head_blocks(d->h, d->w), hw = d->h * d->w;
     const HeadArgs a{d->f, d->lin, reinterpret_cast<double*>(d->temp), d->P, d->C, hw, nb};
     hipLaunchKernelGGL(k_lpips_head, dim3(nb, d->P), dim3(256), 0, s, a);
@@ -308,3 +310,88 @@ hipError_t launch_lpips_head(const TexGSLpipsHead* d, hipStream_t s) {
                        d->layer);
     return hipGetLastError();
 }
+
+// the strides of a [B, Cn, h, w] view in floats: all zero (dense), or no two elements on one address and B img below 2^62
+int check_conv_strides(const char* name, int64_t row, int64_t chan, int64_t img, int64_t B, int64_t Cn, int64_t h, int64_t w) {
+    if (row == 0 && chan == 0 && img == 0) return 0;
+    if (row < w || chan < 0 || img < 0 || chan / h < row || img / Cn < chan || img > (1ll << 62) / B) {
+        return failf("%s_row, %s_chan, %s_img must be all 0 (dense) or row >= width, chan >= rows x row, img >= channels x chan, "
+                     "B x img <= 2^62; got %lld, %lld, %lld", name, name, name, (long long)row, (long long)chan, (long long)img);
+    }
+    return 0;
+}
+
+int check_lpips_head_size(int32_t P, int32_t h, int32_t w) {
+    if (P < 1 || P > 65535) return failf("P must be in [1,65535], got %d", (int)P);
+    if (h < 1 || w < 1) return fail_msg("h and w must be at least 1");
+    if ((int64_t)h * w >= (1ll << 31)) return fail_msg("map too large: h w must be below 2^31");
+    return 0;
+}
+
+extern "C" {
+
+// include/texgs_lpips.h: every argument is checked before the first launch, so a refused call has changed nothing
+static int check_lpips_precision(int32_t precision) {
+    if (precision == TEXGS_LPIPS_FP32) return 0;
+    if (precision == TEXGS_LPIPS_BF16X3) return fail_msg("precision TEXGS_LPIPS_BF16X3 is not built into this library: use TEXGS_LPIPS_FP32");
+    return failf("unknown precision %d (TEXGS_LPIPS_FP32 is 0)", (int)precision);
+}
+
+static int check_conv_channels(int32_t Cin, int32_t Cout, int32_t precision) {
+    if (int r = check_lpips_precision(precision)) return r;
+    if (Cin < 1 || Cin > TEXGS_CONV_MAX_CHANNELS) return failf("Cin must be in [1,512], got %d", (int)Cin);
+    if (Cout < 16 || Cout > TEXGS_CONV_MAX_CHANNELS || Cout % 16) return failf("Cout must be a multiple of 16 in [16,512], got %d", (int)Cout);
+    return 0;
+}
+
+size_t texgs_conv3x3_packed_bytes(int32_t Cin, int32_t Cout, int32_t precision) {
+    return check_conv_channels(Cin, Cout, precision) ? 0 : conv3x3_packed_bytes(Cin, Cout);
+}
+
+int texgs_conv3x3_pack(const float* w, int32_t Cin, int32_t Cout, int32_t precision, void* packed, void* stream) {
+    if (int r = check_conv_channels(Cin, Cout, precision)) return r;
+    if (!w || !packed) return fail_msg("NULL argument (w or packed)");
+    if ((uintptr_t)w & 3) return fail_msg("w must be 4-byte aligned");
+    if ((uintptr_t)packed & 15) return fail_msg("packed must be 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    return launched("conv3x3_pack", launch_conv3x3_pack(w, Cin, Cout, packed, s), s, false);
+}
+
+int texgs_conv3x3(const TexGSConv3x3* d, void* stream) {
+    if (!d) return fail_msg("conv descriptor is NULL");
+    if (int r = check_conv_channels(d->Cin, d->Cout, d->precision)) return r;
+    if ((d->relu != 0 && d->relu != 1) || (d->pool_in != 0 && d->pool_in != 1)) return fail_msg("relu and pool_in must be 0 or 1");
+    if (d->B < 1 || d->B > TEXGS_CONV_MAX_BATCH) return failf("B must be in [1,65535], got %d", (int)d->B);
+    if (d->H < 1 || d->W < 1) return fail_msg("H and W must be at least 1");
+    const int64_t Ho = d->pool_in ? d->H / 2 : d->H, Wo = d->pool_in ? d->W / 2 : d->W;
+    if (Ho < 1 || Wo < 1) return fail_msg("H and W must be at least 2 with pool_in: the pooled image would be empty");
+    if ((int64_t)d->B * Ho * Wo >= (1ll << 31)) return fail_msg("too many output pixels: B Ho Wo must be below 2^31");
+    const int64_t tiles = ((Wo + TEXGS_CONV_TILE_W - 1) / TEXGS_CONV_TILE_W) * ((Ho + TEXGS_CONV_TILE_H - 1) / TEXGS_CONV_TILE_H);
+    if (tiles >= (1ll << 24)) return fail_msg("too many pixel tiles: an image must have fewer than 2^24 tiles of 8 x 32 output pixels");
+    if (int r = check_conv_strides("x", d->x_row, d->x_chan, d->x_img, d->B, d->Cin, d->H, d->W)) return r;
+    if (int r = check_conv_strides("y", d->y_row, d->y_chan, d->y_img, d->B, d->Cout, Ho, Wo)) return r;
+    if (!d->x || !d->y || !d->bias) return fail_msg("NULL argument (x, y or bias)");
+    if (!d->packed) return fail_msg("NULL argument (packed)");
+    if ((!d->in_scale) != (!d->in_shift)) return fail_msg("in_scale and in_shift must be both NULL or both set");
+    if (((uintptr_t)d->x | (uintptr_t)d->y | (uintptr_t)d->bias | (uintptr_t)d->in_scale | (uintptr_t)d->in_shift) & 3)
+        return fail_msg("x, y, bias, in_scale and in_shift must be 4-byte aligned");
+    if ((uintptr_t)d->packed & 15) return fail_msg("packed must be 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    return launched("conv3x3", launch_conv3x3(d, s), s, false);
+}
+
+size_t texgs_lpips_head_temp_bytes(int32_t P, int32_t h, int32_t w) { return check_lpips_head_size(P, h, w) ? 0 : lpips_head_temp_bytes(P, h, w); }
+
+int texgs_lpips_head(const TexGSLpipsHead* d, void* stream) {
+    if (!d) return fail_msg("head descriptor is NULL");
+    if (int r = check_lpips_head_size(d->P, d->h, d->w)) return r;
+    if (d->C < 1 || d->C > TEXGS_CONV_MAX_CHANNELS) return failf("C must be in [1,512], got %d", (int)d->C);
+    if (d->layer < 0 || d->layer >= TEXGS_LPIPS_LAYERS) return failf("layer must be in [0,4], got %d", (int)d->layer);
+    if (!d->f || !d->lin || !d->out || !d->temp) return fail_msg("NULL argument (f, lin, out or temp)");
+    if (((uintptr_t)d->f | (uintptr_t)d->lin) & 3) return fail_msg("f and lin must be 4-byte aligned");
+    if (((uintptr_t)d->out | (uintptr_t)d->temp) & 7) return fail_msg("out and temp must be 8-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    return launched("lpips_head", launch_lpips_head(d, s), s, false);
+}
+
+}  // extern "C"

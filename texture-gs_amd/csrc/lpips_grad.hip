@@ -10,6 +10,9 @@
 //   gradient of (a, b) is the first image's gradient of (b, a) bit for bit.  lin[c] and gbar[p] are wave-uniform (scalar loads).
 // GATE  k_lpips_gate: 16 bytes per lane in a grid-stride loop; the n % 4 trailing elements go one per thread of the first block.
 #include "common.h"
+#include "lpips_checks.h"
+#include "texgs_lpips.h"
+#include "texgs_lpips_grad.h"
 
 namespace {
 
@@ -114,7 +117,7 @@ constexpr int LP_GATE_MAX_BLOCKS = 4096;
 
 }  // namespace
 
-hipError_t launch_lpips_head_backward(const TexGSLpipsHeadBackward* d, hipStream_t s) {
+static hipError_t launch_lpips_head_backward(const TexGSLpipsHeadBackward* d, hipStream_t s) {
     const long long hw = (long long)d->h * d->w;
     const bool dense = !d->g_row && !d->g_chan && !d->g_img;
     const long long gr = dense ? d->w : d->g_row, gc = dense ? gr * d->h : d->g_chan, gi = dense ? gc * d->C : d->g_img;
@@ -123,9 +126,38 @@ hipError_t launch_lpips_head_backward(const TexGSLpipsHeadBackward* d, hipStream
     return hipGetLastError();
 }
 
-hipError_t launch_lpips_gate(float* G, const float* y, long long n, hipStream_t s) {
+static hipError_t launch_lpips_gate(float* G, const float* y, long long n, hipStream_t s) {
     const long long nvec = n / 4, blocks = (nvec + 255) / 256;
     const unsigned grid = (unsigned)(blocks < 1 ? 1 : blocks > LP_GATE_MAX_BLOCKS ? LP_GATE_MAX_BLOCKS : blocks);
     hipLaunchKernelGGL(k_lpips_gate, dim3(grid), dim3(256), 0, s, G, y, nvec, n);
     return hipGetLastError();
 }
+
+extern "C" {
+
+// include/texgs_lpips_grad.h: every argument is checked before the launch, so a refused call has changed nothing
+int texgs_lpips_head_backward(const TexGSLpipsHeadBackward* d, void* stream) {
+    if (!d) return fail_msg("head backward descriptor is NULL");
+    if (int r = check_lpips_head_size(d->P, d->h, d->w)) return r;
+    if (d->C < 1 || d->C > TEXGS_CONV_MAX_CHANNELS) return failf("C must be in [1,512], got %d", (int)d->C);
+    if (d->wrt < 1 || d->wrt > (TEXGS_LPIPS_WRT_FIRST | TEXGS_LPIPS_WRT_PARTNER))
+        return failf("wrt must be 1 (first images), 2 (partners) or 3 (both), got %d", (int)d->wrt);
+    if (d->g_next && (d->h < 2 || d->w < 2)) return fail_msg("g_next needs h and w of at least 2: the pooled map would be empty");
+    const int64_t Bg = d->wrt == 3 ? 2 * (int64_t)d->P : d->P;
+    if (int r = check_conv_strides("g", d->g_row, d->g_chan, d->g_img, Bg, d->C, d->h, d->w)) return r;
+    if (!d->f || !d->lin || !d->gbar || !d->G) return fail_msg("NULL argument (f, lin, gbar or G)");
+    if (((uintptr_t)d->f | (uintptr_t)d->lin | (uintptr_t)d->gbar | (uintptr_t)d->g_next | (uintptr_t)d->G) & 3)
+        return fail_msg("f, lin, gbar, g_next and G must be 4-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    return launched("lpips_head_backward", launch_lpips_head_backward(d, s), s, false);
+}
+
+int texgs_lpips_gate(float* G, const float* y, int64_t n, void* stream) {
+    if (n < 1 || n >= (1ll << 40)) return failf("n must be in [1,2^40), got %lld", (long long)n);
+    if (!G || !y) return fail_msg("NULL argument (G or y)");
+    if (((uintptr_t)G | (uintptr_t)y) & 15) return fail_msg("G and y must be 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    return launched("lpips_gate", launch_lpips_gate(G, y, n, s), s, false);
+}
+
+}  // extern "C"

@@ -13,6 +13,7 @@
 // 7-tap sums (rows into LDS as fp64, then columns); LDS 60 224 B per block, two blocks per CU.  Each block writes its NSUM partial
 // sums to temp[k][block]; k_metrics_reduce (one block) adds them in a fixed order.  No atomics: a row is the same bits every run.
 #include "common.h"
+#include "abi_support.h"
 
 namespace {
 
@@ -167,13 +168,13 @@ inline long long metrics_blocks(int H, int W) { return (long long)((W + MT - 1) 
 
 static_assert(NSUM == TEXGS_METRICS_MAE_DEN + 1 && NSUM <= TEXGS_METRICS_PIXELS, "row layout of texgs.h");
 
-size_t eval_metrics_temp_bytes(int H, int W) {
+static size_t eval_metrics_temp_bytes(int H, int W) {
     if (H <= 0 || W <= 0) return 0;
     return (size_t)metrics_blocks(H, W) * NSUM * sizeof(double);
 }
 
-// H, W >= 7, the tile count below 2^31 and the pointers are the caller's (abi.hip) to check
-hipError_t launch_eval_metrics(const float* image, const float* gt_image, const float* norm, const float* gt_norm, const float* alpha, int H,
+// H, W >= 7, the tile count below 2^31 and the pointers are checked by texgs_eval_metrics below
+static hipError_t launch_eval_metrics(const float* image, const float* gt_image, const float* norm, const float* gt_norm, const float* alpha, int H,
                         int W, int clamp01, void* temp, double* row, hipStream_t s) {
     const int tiles_x = (W + MT - 1) / MT, nblocks = (int)metrics_blocks(H, W);
     hipLaunchKernelGGL(k_metrics, dim3(nblocks), dim3(256), 0, s, H, W, tiles_x, nblocks, clamp01, image, gt_image, norm, gt_norm,
@@ -181,3 +182,19 @@ hipError_t launch_eval_metrics(const float* image, const float* gt_image, const 
     hipLaunchKernelGGL(k_metrics_reduce, dim3(1), dim3(256), 0, s, H, W, nblocks, (const double*)temp, row);
     return hipGetLastError();
 }
+
+extern "C" {
+
+size_t texgs_eval_metrics_temp_bytes(int32_t H, int32_t W) { return eval_metrics_temp_bytes(H, W); }
+
+int texgs_eval_metrics(const float* image, const float* gt_image, const float* norm, const float* gt_norm, const float* alpha,
+                       int32_t H, int32_t W, int32_t clamp01, void* temp, double* row, void* stream) {
+    if (!image || !gt_image || !temp || !row) return fail_msg("NULL argument");
+    if (H < 7 || W < 7) return fail_msg("H and W must be at least 7: the 7x7 SSIM window does not fit");
+    if ((!norm) != (!gt_norm)) return fail_msg("norm and gt_norm must be both NULL or both set");
+    if ((((int64_t)W + 31) / 32) * (((int64_t)H + 31) / 32) >= (1ll << 31)) return fail_msg("image too large: 2^31 tiles or more");
+    hipStream_t s = (hipStream_t)stream;
+    return launched("eval_metrics", launch_eval_metrics(image, gt_image, norm, gt_norm, alpha, H, W, clamp01 != 0, temp, row, s), s, false);
+}
+
+}  // extern "C"

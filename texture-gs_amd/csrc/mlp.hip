@@ -28,6 +28,8 @@
 //   The three weight gradients stay in registers (192 VGPRs) across a workgroup's tiles; each workgroup writes its partial sums once,
 //   k_mlp_backward_reduce adds them in workgroup order.  No atomics: two calls give the same bits.
 #include "common.h"
+#include "abi_support.h"
+#include "texgs_mlp.h"
 
 namespace {
 
@@ -317,18 +319,18 @@ int pad16(int k) { return (k + 15) / 16 * 16; }
 
 }  // namespace
 
-size_t mlp_param_count(const TexGSMlp* m) {
+static size_t mlp_param_count(const TexGSMlp* m) {
     return (size_t)ML_H * pad16(m->n_in) + (size_t)(m->n_hidden_layers - 1) * ML_MAT + (size_t)pad16(m->n_out) * ML_H;
 }
 
-size_t mlp_forward_temp_bytes() { return (size_t)ML_FWD_MATS * ML_MAT_BYTES; }
+static size_t mlp_forward_temp_bytes() { return (size_t)ML_FWD_MATS * ML_MAT_BYTES; }
 
 static int mlp_backward_blocks(int N) {
     const int t = (N + ML_BT - 1) / ML_BT;
     return t < TEXGS_MLP_BACKWARD_MAX_WORKGROUPS ? (t < 1 ? 1 : t) : TEXGS_MLP_BACKWARD_MAX_WORKGROUPS;
 }
 
-size_t mlp_backward_temp_bytes(int N) {
+static size_t mlp_backward_temp_bytes(int N) {
     return (size_t)ML_BWD_MATS * ML_MAT_BYTES + (size_t)mlp_backward_blocks(N) * 3 * ML_MAT_BYTES;
 }
 
@@ -340,7 +342,7 @@ static void mlp_mats(const TexGSMlp* m, MlpPackMat& w1, MlpPackMat& w2, MlpPackM
     wo = {ML_H * pin + (m->n_hidden_layers - 1) * ML_MAT, pout, ML_H, 0};
 }
 
-hipError_t launch_mlp_forward(const TexGSMlp* m, const float* params, const float* x, int N, float* y, void* temp, hipStream_t s) {
+static hipError_t launch_mlp_forward(const TexGSMlp* m, const float* params, const float* x, int N, float* y, void* temp, hipStream_t s) {
     if (N <= 0) return hipSuccess;
     MlpPackMat w1, w2, wo;
     mlp_mats(m, w1, w2, wo);
@@ -352,7 +354,7 @@ hipError_t launch_mlp_forward(const TexGSMlp* m, const float* params, const floa
     return hipGetLastError();
 }
 
-hipError_t launch_mlp_backward(const TexGSMlp* m, const float* params, const float* x, const float* dy, int N, float* dx, float* d_params,
+static hipError_t launch_mlp_backward(const TexGSMlp* m, const float* params, const float* x, const float* dy, int N, float* dx, float* d_params,
                                void* temp, hipStream_t s) {
     LaunchStatus st;
     if (N <= 0) {                                          // no points: every gradient is zero
@@ -377,3 +379,54 @@ hipError_t launch_mlp_backward(const TexGSMlp* m, const float* params, const flo
     }
     return st.after_launches();
 }
+
+extern "C" {
+
+// include/texgs_mlp.h: the shape, by name
+static int check_mlp(const TexGSMlp* m) {
+    if (!m) return fail_msg("mlp is NULL");
+    const char* what = nullptr;
+    int v = 0;
+    if (m->n_neurons != TEXGS_MLP_WIDTH) { what = "n_neurons must be 128"; v = m->n_neurons; }
+    else if (m->n_hidden_layers < 1 || m->n_hidden_layers > TEXGS_MLP_MAX_HIDDEN_LAYERS) { what = "n_hidden_layers must be 1 or 2"; v = m->n_hidden_layers; }
+    else if (m->n_in < 1 || m->n_in > TEXGS_MLP_WIDTH) { what = "n_in must be in [1,128]"; v = m->n_in; }
+    else if (m->n_out < 1 || m->n_out > TEXGS_MLP_WIDTH) { what = "n_out must be in [1,128]"; v = m->n_out; }
+    if (!what) return 0;
+    return failf("the fused MLP does not support this shape: %s, got %d", what, v);
+}
+
+static int check_mlp_call(const TexGSMlp* m, int32_t N, const void* params, const void* temp) {
+    if (int r = check_mlp(m)) return r;
+    if (N < 0) return fail_msg("N < 0");
+    if (N > INT32_MAX - TEXGS_MLP_FORWARD_TILE) return fail_msg("N too large: the tile count is a 32-bit integer");
+    if (!params || !temp) return fail_msg("NULL argument (params or temp)");
+    if ((uintptr_t)params & 3) return fail_msg("params must be 4-byte aligned");
+    if ((uintptr_t)temp & 15) return fail_msg("temp must be 16-byte aligned");
+    return 0;
+}
+
+size_t texgs_mlp_param_count(const TexGSMlp* mlp) { return check_mlp(mlp) ? 0 : mlp_param_count(mlp); }
+
+size_t texgs_mlp_forward_temp_bytes(const TexGSMlp* mlp, int32_t N) { return check_mlp(mlp) || N < 0 ? 0 : mlp_forward_temp_bytes(); }
+
+size_t texgs_mlp_backward_temp_bytes(const TexGSMlp* mlp, int32_t N) { return check_mlp(mlp) || N < 0 ? 0 : mlp_backward_temp_bytes(N); }
+
+int texgs_mlp_forward(const TexGSMlp* mlp, const float* params, const float* x, int32_t N, float* y, void* temp, void* stream) {
+    if (int r = check_mlp_call(mlp, N, params, temp)) return r;
+    if (N == 0) return 0;
+    if (!x || !y) return fail_msg("NULL argument (x or y)");
+    if (((uintptr_t)x | (uintptr_t)y) & 3) return fail_msg("x and y must be 4-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    return launched("mlp_forward", launch_mlp_forward(mlp, params, x, N, y, temp, s), s, false);
+}
+
+int texgs_mlp_backward(const TexGSMlp* mlp, const float* params, const float* x, const float* dy, int32_t N, float* dx, float* d_params,
+                       void* temp, void* stream) {
+    if (int r = check_mlp_call(mlp, N, params, temp)) return r;
+    if (N > 0 && (!x || !dy)) return fail_msg("NULL argument (x or dy)");
+    if (((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx | (uintptr_t)d_params) & 3) return fail_msg("x, dy, dx and d_params must be 4-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    return launched("mlp_backward", launch_mlp_backward(mlp, params, x, dy, N, dx, d_params, temp, s), s, false);
+}
+
+}  // extern "C"

@@ -8,6 +8,8 @@
 // copied to the device, nothing allocated, nothing waited for.  Work is cut into chunks of TEXGS_ADAM_CHUNK elements over all the
 // tensors of a launch; a workgroup finds the tensor of its chunk from the prefix and grid-strides over the chunks.
 #include "common.h"
+#include "abi_support.h"
+#include "texgs_optim.h"
 
 namespace {
 
@@ -95,8 +97,8 @@ k_adam_step(AdamArgs a) {
 
 }  // namespace
 
-// One launch over `count` <= TEXGS_ADAM_MAX_TENSORS records (checked by the caller, abi.hip)
-hipError_t launch_adam_step(const TexGSAdamTensor* tensors, int count, int zero_grads, hipStream_t s) {
+// One launch over `count` <= TEXGS_ADAM_MAX_TENSORS records (texgs_adam_step below cuts longer lists)
+static hipError_t launch_adam_step(const TexGSAdamTensor* tensors, int count, int zero_grads, hipStream_t s) {
     if (count < 0 || count > AD_MAX) return hipErrorInvalidValue;
     AdamArgs a;
     uint64_t chunks = 0;
@@ -113,4 +115,25 @@ hipError_t launch_adam_step(const TexGSAdamTensor* tensors, int count, int zero_
     const uint32_t grid = chunks < AD_GRID_CAP ? (uint32_t)chunks : AD_GRID_CAP;
     hipLaunchKernelGGL(k_adam_step, dim3(grid), dim3(AD_BLOCK), 0, s, a);
     return hipGetLastError();
+}
+
+// include/texgs_optim.h: every record is checked before the first launch, so a refused call has changed nothing
+extern "C" int texgs_adam_step(const TexGSAdamTensor* tensors, int32_t count, int32_t zero_grads, void* stream) {
+    if (count < 0) return fail_msg("count < 0");
+    if (count == 0) return 0;
+    if (!tensors) return fail_msg("tensors is NULL");
+    for (int32_t k = 0; k < count; ++k) {
+        const TexGSAdamTensor& t = tensors[k];
+        if (t.numel < 0) return fail_msg("numel < 0");
+        if (t.numel == 0) continue;
+        if (!t.p || !t.g || !t.m || !t.v) return fail_msg("NULL pointer (p, g, m or v) in a record with numel > 0");
+        if (((uintptr_t)t.p | (uintptr_t)t.g | (uintptr_t)t.m | (uintptr_t)t.v) & 3)
+            return fail_msg("p, g, m and v must be 4-byte aligned");
+    }
+    hipStream_t s = (hipStream_t)stream;
+    for (int32_t first = 0; first < count; first += TEXGS_ADAM_MAX_TENSORS) {
+        const int32_t n = count - first < TEXGS_ADAM_MAX_TENSORS ? count - first : TEXGS_ADAM_MAX_TENSORS;
+        if (int r = launched("adam_step", launch_adam_step(tensors + first, n, zero_grads, s), s, false)) return r;
+    }
+    return 0;
 }

@@ -11,6 +11,8 @@
 //     same way, as it does its six outputs, so global memory sees dense dwords only.
 // The regulariser's sum is fp64 in a fixed order: a tree over the workgroup's rows, then one workgroup over the partials.
 #include "common.h"
+#include "abi_support.h"
+#include "texgs_params.h"
 #include "params_math.h"
 
 namespace {
@@ -186,26 +188,110 @@ inline uint32_t params_groups(int32_t n) { return ((uint32_t)n + PB - 1) / PB; }
 
 }  // namespace
 
-size_t params_temp_bytes(int32_t n) { return ((size_t)params_groups(n) * sizeof(double) + 255) & ~(size_t)255; }
+static size_t params_temp_bytes(int32_t n) { return ((size_t)params_groups(n) * sizeof(double) + 255) & ~(size_t)255; }
 
-hipError_t launch_params_activate(const TexGSParamsActivate* a, void* temp, hipStream_t s) {
+static hipError_t launch_params_activate(const TexGSParamsActivate* a, void* temp, hipStream_t s) {
     const uint32_t groups = params_groups(a->n);
     hipLaunchKernelGGL(k_params_activate, dim3(groups), dim3(PB), 0, s, *a, (double*)temp);
     if (a->reg) hipLaunchKernelGGL(k_params_reg_finish, dim3(1), dim3(PB), 0, s, (const double*)temp, groups, (uint32_t)a->n, a->reg);
     return hipGetLastError();
 }
 
-hipError_t launch_params_activate_backward(const TexGSParamsActivateGrad* g, hipStream_t s) {
+static hipError_t launch_params_activate_backward(const TexGSParamsActivateGrad* g, hipStream_t s) {
     hipLaunchKernelGGL(k_params_activate_backward, dim3(params_groups(g->n)), dim3(PB), 0, s, *g);
     return hipGetLastError();
 }
 
-hipError_t launch_params_covariance(const TexGSParamsCovariance* c, hipStream_t s) {
+static hipError_t launch_params_covariance(const TexGSParamsCovariance* c, hipStream_t s) {
     hipLaunchKernelGGL(k_params_covariance, dim3(params_groups(c->n)), dim3(PB), 0, s, *c);
     return hipGetLastError();
 }
 
-hipError_t launch_params_covariance_backward(const TexGSParamsCovarianceGrad* c, hipStream_t s) {
+static hipError_t launch_params_covariance_backward(const TexGSParamsCovarianceGrad* c, hipStream_t s) {
     hipLaunchKernelGGL(k_params_covariance_backward, dim3(params_groups(c->n)), dim3(PB), 0, s, *c);
     return hipGetLastError();
 }
+
+extern "C" {
+
+// include/texgs_params.h: every argument is checked before the first launch, so a refused call has changed nothing
+static int check_params_epsilon(float e) {
+    if (!(e > 0.0f && e < 0.5f)) return fail_msg("epsilon must lie in (0, 0.5)");
+    return 0;
+}
+
+static int check_params_modifier(float m) {
+    if (!(m > 0.0f) || m - m != 0.0f) return fail_msg("scale_modifier must be finite and positive");
+    return 0;
+}
+
+size_t texgs_params_temp_bytes(int32_t n) { return n <= 0 ? 0 : params_temp_bytes(n); }
+
+int texgs_params_activate(const TexGSParamsActivate* a, void* temp, size_t temp_bytes, void* stream) {
+    if (!a) return fail_msg("activate descriptor is NULL");
+    if (a->n < 0) return fail_msg("n < 0");
+    if (a->reg) {
+        if (int r = check_params_epsilon(a->epsilon)) return r;
+        if (a->n == 0) return fail_msg("reg with n = 0: a mean over nothing");
+    }
+    if (a->n == 0) return 0;
+    if (!a->scales && !a->rotations && !a->opacities && !a->reg)
+        return fail_msg("no output requested (scales, rotations, opacities and reg are all NULL)");
+    if ((a->scales && !a->scaling) || (a->rotations && !a->rotation) || ((a->opacities || a->reg) && !a->opacity))
+        return fail_msg("NULL argument (scaling, rotation or opacity: the input of a requested output)");
+    if (a->reg && !temp) return fail_msg("NULL argument (temp, needed with reg)");
+    if (((uintptr_t)a->scaling | (uintptr_t)a->opacity | (uintptr_t)a->scales | (uintptr_t)a->opacities | (uintptr_t)a->reg) & 3)
+        return fail_msg("scaling, opacity, scales, opacities and reg must be 4-byte aligned");
+    if (((uintptr_t)a->rotation | (uintptr_t)a->rotations) & 15) return fail_msg("rotation and rotations must be 16-byte aligned");
+    if (a->reg && ((uintptr_t)temp & 7)) return fail_msg("temp must be 8-byte aligned");
+    if (a->reg && temp_bytes < params_temp_bytes(a->n)) return fail_msg("temp is smaller than texgs_params_temp_bytes");
+    hipStream_t s = (hipStream_t)stream;
+    return launched("params_activate", launch_params_activate(a, temp, s), s, false);
+}
+
+int texgs_params_activate_backward(const TexGSParamsActivateGrad* g, void* stream) {
+    if (!g) return fail_msg("activate backward descriptor is NULL");
+    if (g->n < 0) return fail_msg("n < 0");
+    if (g->g_reg)
+        if (int r = check_params_epsilon(g->epsilon)) return r;
+    if (g->n == 0) return 0;
+    if (!g->d_scaling && !g->d_rotation && !g->d_opacity)
+        return fail_msg("no output requested (d_scaling, d_rotation and d_opacity are all NULL)");
+    if ((g->d_scaling && g->g_scales && !g->scales) || (g->d_rotation && g->g_rotations && !g->rotation) ||
+        (g->d_opacity && (g->g_opacities || g->g_reg) && !g->opacities))
+        return fail_msg("NULL argument (scales, rotation or opacities: read for a requested output with an upstream gradient)");
+    if (((uintptr_t)g->scales | (uintptr_t)g->opacities | (uintptr_t)g->g_scales | (uintptr_t)g->g_opacities | (uintptr_t)g->g_reg |
+         (uintptr_t)g->d_scaling | (uintptr_t)g->d_opacity) & 3)
+        return fail_msg("scales, opacities, g_scales, g_opacities, g_reg, d_scaling and d_opacity must be 4-byte aligned");
+    if (((uintptr_t)g->rotation | (uintptr_t)g->g_rotations | (uintptr_t)g->d_rotation) & 15)
+        return fail_msg("rotation, g_rotations and d_rotation must be 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    return launched("params_activate_backward", launch_params_activate_backward(g, s), s, false);
+}
+
+int texgs_params_covariance(const TexGSParamsCovariance* c, void* stream) {
+    if (!c) return fail_msg("covariance descriptor is NULL");
+    if (c->n < 0) return fail_msg("n < 0");
+    if (int r = check_params_modifier(c->scale_modifier)) return r;
+    if (c->n == 0) return 0;
+    if (!c->scaling || !c->rotation || !c->cov) return fail_msg("NULL argument (scaling, rotation or cov)");
+    if (((uintptr_t)c->scaling | (uintptr_t)c->cov) & 3) return fail_msg("scaling and cov must be 4-byte aligned");
+    if ((uintptr_t)c->rotation & 15) return fail_msg("rotation must be 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    return launched("params_covariance", launch_params_covariance(c, s), s, false);
+}
+
+int texgs_params_covariance_backward(const TexGSParamsCovarianceGrad* c, void* stream) {
+    if (!c) return fail_msg("covariance backward descriptor is NULL");
+    if (c->n < 0) return fail_msg("n < 0");
+    if (int r = check_params_modifier(c->scale_modifier)) return r;
+    if (c->n == 0) return 0;
+    if (!c->d_scaling && !c->d_rotation) return fail_msg("no output requested (d_scaling and d_rotation are both NULL)");
+    if (!c->scaling || !c->rotation) return fail_msg("NULL argument (scaling or rotation)");
+    if (((uintptr_t)c->scaling | (uintptr_t)c->g_cov | (uintptr_t)c->d_scaling) & 3) return fail_msg("scaling, g_cov and d_scaling must be 4-byte aligned");
+    if (((uintptr_t)c->rotation | (uintptr_t)c->d_rotation) & 15) return fail_msg("rotation and d_rotation must be 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    return launched("params_covariance_backward", launch_params_covariance_backward(c, s), s, false);
+}
+
+}  // extern "C"

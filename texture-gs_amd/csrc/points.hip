@@ -10,6 +10,7 @@
 // Every dependency is a kernel boundary on the caller's stream: no spinning, no grid-wide barrier.  Every result is written by
 // ordinary vector stores / vector atomics from device code.
 #include "common.h"
+#include "abi_support.h"
 #include "wave_ops.h"
 
 namespace {
@@ -341,9 +342,9 @@ KnnTemp knn_temp(void* base, uint32_t n) {
 
 }  // namespace
 
-size_t knn3_temp_bytes(int n) { return knn_temp(nullptr, (uint32_t)(n > 0 ? n : 1)).bytes; }
+static size_t knn3_temp_bytes(int n) { return knn_temp(nullptr, (uint32_t)(n > 0 ? n : 1)).bytes; }
 
-hipError_t launch_knn3_mean_dist2(const float* xyz, int n_, float* mean_d2, void* temp, hipStream_t s) {
+static hipError_t launch_knn3_mean_dist2(const float* xyz, int n_, float* mean_d2, void* temp, hipStream_t s) {
     const uint32_t n = (uint32_t)n_;
     const KnnTemp t = knn_temp(temp, n);
     const uint32_t nb = (n + PT_BLOCK - 1) / PT_BLOCK;
@@ -358,11 +359,11 @@ hipError_t launch_knn3_mean_dist2(const float* xyz, int n_, float* mean_d2, void
 }
 
 // temp: m, px, py, pz (n floats each, padded to 256 bytes: a multiple of 4 points), then k x FPS_SUB 64-bit slots
-size_t fps_temp_bytes(int n, int k) {
+static size_t fps_temp_bytes(int n, int k) {
     return 4 * align256((size_t)(n > 0 ? n : 1) * 4) + align256((size_t)(k > 0 ? k : 1) * 8 * FPS_SUB);
 }
 
-hipError_t launch_farthest_points(const float* xyz, int n_, int k_, int start, int32_t* idx, void* temp, hipStream_t s) {
+static hipError_t launch_farthest_points(const float* xyz, int n_, int k_, int start, int32_t* idx, void* temp, hipStream_t s) {
     const uint32_t n = (uint32_t)n_, k = (uint32_t)k_;
     const size_t plane = align256((size_t)n * 4);
     float* m = (float*)temp;
@@ -385,6 +386,30 @@ hipError_t launch_farthest_points(const float* xyz, int n_, int k_, int start, i
                        (uint32_t)start, idx);
     return hipGetLastError();
 }
+
+extern "C" {
+
+size_t texgs_knn3_temp_bytes(int32_t n) { return knn3_temp_bytes(n); }
+
+int texgs_knn3_mean_dist2(const float* xyz, int32_t n, float* mean_d2, void* temp, void* stream) {
+    if (n < 4) return fail_msg("n < 4: three nearest other points need at least four points");
+    if (!xyz || !mean_d2 || !temp) return fail_msg("NULL argument");
+    hipStream_t s = (hipStream_t)stream;
+    return launched("knn3_mean_dist2", launch_knn3_mean_dist2(xyz, n, mean_d2, temp, s), s, false);
+}
+
+size_t texgs_fps_temp_bytes(int32_t n, int32_t k) { return fps_temp_bytes(n, k); }
+
+int texgs_farthest_points(const float* xyz, int32_t n, int32_t k, int32_t start, int32_t* idx, void* temp, void* stream) {
+    if (n < 1) return fail_msg("n < 1");
+    if (k < 1 || k > n) return fail_msg("k must be in [1, n]");
+    if (start < 0 || start >= n) return fail_msg("start must be in [0, n)");
+    if (!xyz || !idx || !temp) return fail_msg("NULL argument");
+    hipStream_t s = (hipStream_t)stream;
+    return launched("farthest_points", launch_farthest_points(xyz, n, k, start, idx, temp, s), s, false);
+}
+
+}  // extern "C"
 
 #ifdef TEXGS_POINTS_STATS
 // Debug build only: read (and optionally zero) the search counters; synchronises the device.

@@ -16,6 +16,8 @@
 // host decides that per operand (the `wide_*` bits), so the branch is uniform.
 // Grid: 256 threads, min(quads / 256, TEXGS_PRESENT_MAX_WORKGROUPS) workgroups, grid-strided.
 #include "common.h"
+#include "abi_support.h"
+#include "texgs_present.h"
 
 #include <math.h>
 
@@ -300,8 +302,8 @@ QuadOut quad_out(uint8_t* u8, float* hwc4, float* chw, uint32_t P, int u8_channe
 
 }  // namespace
 
-// (the arguments were validated by abi.hip)
-hipError_t launch_present(const TexGSPresent* p, hipStream_t s) {
+// (the arguments of the three launchers are validated by the entry points below)
+static hipError_t launch_present(const TexGSPresent* p, hipStream_t s) {
     const uint32_t P = (uint32_t)p->height * (uint32_t)p->width;
     PresentArgs a;
     a.src = p->src; a.alpha = p->alpha; a.bg = p->background;
@@ -313,12 +315,12 @@ hipError_t launch_present(const TexGSPresent* p, hipStream_t s) {
     return hipGetLastError();
 }
 
-size_t depth_colour_temp_bytes(int H, int W) {
+static size_t depth_colour_temp_bytes(int H, int W) {
     const uint32_t P = (uint32_t)H * (uint32_t)W;
     return (size_t)quad_grid((P + PQ - 1) / PQ) * 2 * sizeof(float);
 }
 
-hipError_t launch_depth_colour(const TexGSDepthColour* d, void* temp, hipStream_t s) {
+static hipError_t launch_depth_colour(const TexGSDepthColour* d, void* temp, hipStream_t s) {
     const uint32_t P = (uint32_t)d->height * (uint32_t)d->width;
     const int grid = quad_grid((P + PQ - 1) / PQ);
     DepthArgs a;
@@ -332,9 +334,70 @@ hipError_t launch_depth_colour(const TexGSDepthColour* d, void* temp, hipStream_
     return hipGetLastError();
 }
 
-hipError_t launch_cube_cross(const TexGSCubeCross* c, hipStream_t s) {
+static hipError_t launch_cube_cross(const TexGSCubeCross* c, hipStream_t s) {
     const uint32_t R = (uint32_t)c->res;
     const int wide = R % 4 == 0 && aligned16(c->texture);
     hipLaunchKernelGGL(k_cube_cross, dim3(quad_grid(3u * R * R)), dim3(PB), 0, s, c->texture, c->out, R, wide);
     return hipGetLastError();
 }
+
+extern "C" {
+
+// include/texgs_present.h: every argument is checked before the first launch, so a refused call has changed nothing
+static int check_present_image(int32_t H, int32_t W) {
+    if (H <= 0 || W <= 0) return fail_msg("height and width must be positive");
+    if ((long long)H * W >= (1ll << 31)) return fail_msg("image too large: height * width must be below 2^31");
+    return 0;
+}
+
+static int check_present_outputs(const uint8_t* u8, int32_t u8_channels, const float* hwc4, const float* chw) {
+    if (!u8 && !hwc4 && !chw) return fail_msg("no output requested (out_u8, out_hwc4 and out_chw are all NULL)");
+    if (u8) {
+        if (u8_channels != 3 && u8_channels != 4) return fail_msg("u8_channels must be 3 or 4");
+        if ((uintptr_t)u8 & (u8_channels == 4 ? 15 : 3)) return fail_msg("out_u8 must be 4-byte aligned with 3 channels, 16-byte aligned with 4");
+    }
+    if ((uintptr_t)hwc4 & 15) return fail_msg("out_hwc4 must be 16-byte aligned");
+    if ((uintptr_t)chw & 3) return fail_msg("out_chw must be 4-byte aligned");
+    return 0;
+}
+
+int texgs_present(const TexGSPresent* p, void* stream) {
+    if (!p) return fail_msg("present descriptor is NULL");
+    if (int r = check_present_image(p->height, p->width)) return r;
+    if (!p->src) return fail_msg("NULL argument (src)");
+    if (p->channels != 1 && p->channels != 3) return fail_msg("channels must be 1 or 3");
+    if (p->flags & ~(TEXGS_PRESENT_AFFINE | TEXGS_PRESENT_COMPOSITE | TEXGS_PRESENT_SWAP_RB)) return fail_msg("unknown bit in flags");
+    if ((p->flags & TEXGS_PRESENT_COMPOSITE) && !p->alpha) return fail_msg("composite mode needs alpha");
+    if (int r = check_present_outputs(p->out_u8, p->u8_channels, p->out_hwc4, p->out_chw)) return r;
+    if (((uintptr_t)p->src | (uintptr_t)p->alpha | (uintptr_t)p->background) & 3) return fail_msg("src, alpha and background must be 4-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    return launched("present", launch_present(p, s), s, false);
+}
+
+size_t texgs_depth_colour_temp_bytes(int32_t height, int32_t width) {
+    return check_present_image(height, width) ? 0 : depth_colour_temp_bytes(height, width);
+}
+
+int texgs_depth_colour(const TexGSDepthColour* d, void* temp, size_t temp_bytes, void* stream) {
+    if (!d) return fail_msg("depth descriptor is NULL");
+    if (int r = check_present_image(d->height, d->width)) return r;
+    if (!d->depth || !d->lut || !temp) return fail_msg("NULL argument (depth, lut or temp)");
+    if (d->flags & ~TEXGS_PRESENT_SWAP_RB) return fail_msg("unknown bit in flags (the depth picture reads TEXGS_PRESENT_SWAP_RB only)");
+    if (int r = check_present_outputs(d->out_u8, d->u8_channels, d->out_hwc4, d->out_chw)) return r;
+    if (((uintptr_t)d->depth | (uintptr_t)d->mask | (uintptr_t)d->range | (uintptr_t)temp) & 3)
+        return fail_msg("depth, mask, range and temp must be 4-byte aligned");
+    if (temp_bytes < depth_colour_temp_bytes(d->height, d->width)) return fail_msg("temp is smaller than texgs_depth_colour_temp_bytes");
+    hipStream_t s = (hipStream_t)stream;
+    return launched("depth_colour", launch_depth_colour(d, temp, s), s, false);
+}
+
+int texgs_cube_cross(const TexGSCubeCross* c, void* stream) {
+    if (!c) return fail_msg("cross descriptor is NULL");
+    if (c->res < 1 || c->res > 7168) return fail_msg("res must be in [1,7168]");
+    if (!c->texture || !c->out) return fail_msg("NULL argument (texture or out)");
+    if (((uintptr_t)c->texture | (uintptr_t)c->out) & 3) return fail_msg("texture and out must be 4-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    return launched("cube_cross", launch_cube_cross(c, s), s, false);
+}
+
+}  // extern "C"

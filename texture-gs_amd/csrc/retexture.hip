@@ -13,6 +13,8 @@
 // bytes, through the caches: neighbouring texels share them.  No LDS, no atomics.
 // In place (out_tex == old_tex) is safe: a thread loads its own old texels before it stores them, and nobody else reads them.
 #include "common.h"
+#include "abi_support.h"
+#include "texgs_retexture.h"
 #include "retexture_math.h"
 
 namespace {
@@ -155,7 +157,7 @@ inline uint32_t texels(int32_t R) { return 6u * (uint32_t)R * (uint32_t)R; }    
 
 }  // namespace
 
-hipError_t launch_retexture_cross(const TexGSRetexCross* c, hipStream_t s) {
+static hipError_t launch_retexture_cross(const TexGSRetexCross* c, hipStream_t s) {
     const uint32_t total = texels(c->R);
     const uint32_t groups = (total + TPT - 1) / TPT;
     const int aligned16 = (((uintptr_t)c->old_tex | (uintptr_t)c->out_tex) & 15) == 0;
@@ -164,8 +166,52 @@ hipError_t launch_retexture_cross(const TexGSRetexCross* c, hipStream_t s) {
     return hipGetLastError();
 }
 
-hipError_t launch_retexture_latlong(const TexGSRetexLatLong* l, hipStream_t s) {
+static hipError_t launch_retexture_latlong(const TexGSRetexLatLong* l, hipStream_t s) {
     const uint32_t total = texels(l->R);
     hipLaunchKernelGGL(k_retexture_latlong, dim3((total + RT - 1) / RT), dim3(RT), 0, s, *l, total);
     return hipGetLastError();
 }
+
+extern "C" {
+
+// include/texgs_retexture.h: every argument is checked before the launch, so a refused call has changed nothing
+static bool ranges_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
+    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+    return pa < pb + b_bytes && pb < pa + a_bytes;
+}
+
+static int check_retexture(const void* src, size_t src_bytes, const float* old_tex, float* out_tex, int32_t R, int32_t mode) {
+    if (R < 1 || R > TEXGS_RETEX_MAX_RES) return fail_msg("R must be in [1,7168]");
+    if (mode < -1 || mode > 3) return fail_msg("mode must be -1, 0, 1, 2 or 3");
+    if (!src) return fail_msg("NULL argument (src)");
+    if (!out_tex) return fail_msg("NULL argument (out_tex)");
+    if (!old_tex && mode != -1) return fail_msg("NULL argument (old_tex): only mode -1 does without the old texture");
+    if (((uintptr_t)old_tex | (uintptr_t)out_tex) & 3) return fail_msg("old_tex and out_tex must be 4-byte aligned");
+    const size_t tex_bytes = 6 * (size_t)R * (size_t)R * 3 * sizeof(float);
+    if (old_tex && old_tex != out_tex && ranges_overlap(old_tex, tex_bytes, out_tex, tex_bytes))
+        return fail_msg("out_tex overlaps old_tex without being equal to it (in place means the same pointer)");
+    if (ranges_overlap(src, src_bytes, out_tex, tex_bytes)) return fail_msg("out_tex overlaps src");
+    return 0;
+}
+
+int texgs_retexture_cross(const TexGSRetexCross* c, void* stream) {
+    if (!c) return fail_msg("retexture cross descriptor is NULL");
+    if (c->r < 1 || c->r > TEXGS_RETEX_MAX_SRC) return fail_msg("r must be in [1,16384]");
+    if (c->order != TEXGS_RETEX_RGB && c->order != TEXGS_RETEX_BGR) return fail_msg("order must be 0 (rgb) or 1 (bgr)");
+    if (int rc = check_retexture(c->src, 36 * (size_t)c->r * (size_t)c->r, c->old_tex, c->out_tex, c->R, c->mode)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    return launched("retexture_cross", launch_retexture_cross(c, s), s, false);
+}
+
+int texgs_retexture_latlong(const TexGSRetexLatLong* l, void* stream) {
+    if (!l) return fail_msg("retexture latlong descriptor is NULL");
+    if (l->h < 1 || l->h > TEXGS_RETEX_MAX_SRC || l->w < 1 || l->w > TEXGS_RETEX_MAX_SRC) return fail_msg("h and w must be in [1,16384]");
+    if (l->src_u8 != 0 && l->src_u8 != 1) return fail_msg("src_u8 must be 0 or 1");
+    if (!l->src_u8 && ((uintptr_t)l->src & 3)) return fail_msg("a float src must be 4-byte aligned");
+    const size_t src_bytes = 3 * (size_t)l->h * (size_t)l->w * (l->src_u8 ? 1 : sizeof(float));
+    if (int rc = check_retexture(l->src, src_bytes, l->old_tex, l->out_tex, l->R, l->mode)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    return launched("retexture_latlong", launch_retexture_latlong(l, s), s, false);
+}
+
+}  // extern "C"

@@ -1,6 +1,7 @@
 // On-device self-test of csrc/wave_ops.h (the DPP / permlane primitives K7's reductions depend on), exported through
 // the C ABI so that a `-m gpu` test pins it on real hardware: every primitive against the plain __shfl_xor formulation.
 #include "common.h"
+#include "abi_support.h"
 #include "wave_ops.h"
 
 namespace {
@@ -43,7 +44,12 @@ k_selftest_waveops(const float* __restrict__ seed, float* __restrict__ out) {
 
 }  // namespace
 
-hipError_t launch_selftest_waveops(const float* seed128, float* out576, hipStream_t s) {
+static hipError_t launch_selftest_waveops(const float* seed128, float* out576, hipStream_t s) {
     hipLaunchKernelGGL(k_selftest_waveops, dim3(1), dim3(64), 0, s, seed128, out576);
     return hipGetLastError();
+}
+
+extern "C" int texgs_selftest_waveops(const float* seed128, float* out576, void* stream) {
+    if (!seed128 || !out576) return fail_msg("NULL argument");
+    return launched("selftest_waveops", launch_selftest_waveops(seed128, out576, (hipStream_t)stream), (hipStream_t)stream, false);
 }

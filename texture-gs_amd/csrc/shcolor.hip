@@ -15,6 +15,8 @@
 // (k_sh_colors_deg4 below), which measured faster; the backward keeps a row's 25 t_k together and stays one pass.  The degree is a
 // template argument (every basis index a constant); the layout, the mode and K are wave-uniform run-time values.  Offsets are 64-bit.
 #include "common.h"
+#include "abi_support.h"
+#include "texgs_shcolor.h"
 #include "shcolor_math.h"
 
 namespace {
@@ -269,8 +271,8 @@ inline uint32_t sh_groups(int32_t n) { return ((uint32_t)n + SB - 1) / SB; }
 
 }  // namespace
 
-// 1 <= count <= TEXGS_SH_COLORS_MAX_VIEWS, n >= 1 and everything else validated by the caller (abi.hip)
-hipError_t launch_sh_colors(const TexGSShColors* c, const TexGSShColorView* views, int count, hipStream_t s) {
+// 1 <= count <= TEXGS_SH_COLORS_MAX_VIEWS, n >= 1 and everything else validated by check_sh_colors and the entry points below
+static hipError_t launch_sh_colors(const TexGSShColors* c, const TexGSShColorView* views, int count, hipStream_t s) {
     ShColorsArgs a;
     a.c = *c;
     for (int k = 0; k < SV; ++k) a.v[k] = k < count ? views[k] : TexGSShColorView{nullptr, nullptr};
@@ -291,7 +293,7 @@ hipError_t launch_sh_colors(const TexGSShColors* c, const TexGSShColorView* view
     return hipGetLastError();
 }
 
-hipError_t launch_sh_colors_backward(const TexGSShColorsGrad* g, const TexGSShColorGradView* views, int count, hipStream_t s) {
+static hipError_t launch_sh_colors_backward(const TexGSShColorsGrad* g, const TexGSShColorGradView* views, int count, hipStream_t s) {
     ShColorsGradArgs a;
     a.g = *g;
     for (int k = 0; k < SV; ++k) a.v[k] = k < count ? views[k] : TexGSShColorGradView{nullptr, nullptr};
@@ -307,3 +309,66 @@ hipError_t launch_sh_colors_backward(const TexGSShColorsGrad* g, const TexGSShCo
     }
     return hipGetLastError();
 }
+
+extern "C" {
+
+// include/texgs_shcolor.h: every argument is checked before the launch, so a refused call has changed nothing
+static int check_sh_colors(int32_t n, int32_t coeffs, int32_t degree, int32_t layout, int32_t mode, int32_t count, const void* sh,
+                           const void* sh_dc, const void* sh_rest, const void* views) {
+    if (degree < 0 || degree > TEXGS_SH_COLORS_MAX_DEGREE) return fail_msg("degree must be in [0,4]");
+    if (coeffs != 1 && coeffs != 4 && coeffs != 9 && coeffs != 16 && coeffs != 25) return fail_msg("coeffs must be 1, 4, 9, 16 or 25");
+    if ((degree + 1) * (degree + 1) > coeffs) return fail_msg("(degree + 1)^2 exceeds coeffs");
+    if (n < 0) return fail_msg("n < 0");
+    if ((int64_t)n * coeffs * 3 >= (1ll << 31)) return fail_msg("n * coeffs * 3 must be below 2^31");
+    if (layout != TEXGS_SH_LAYOUT_KC && layout != TEXGS_SH_LAYOUT_CK) return fail_msg("layout must be 0 ([n,coeffs,3]) or 1 ([n,3,coeffs])");
+    if (mode != TEXGS_SH_COLORS && mode != TEXGS_SH_EVAL) return fail_msg("mode must be 0 (colours) or 1 (eval_sh)");
+    if (count < 1) return fail_msg("count < 1: at least one view");
+    if (count > TEXGS_SH_COLORS_MAX_VIEWS) return fail_msg("count exceeds TEXGS_SH_COLORS_MAX_VIEWS: several calls");
+    if (mode == TEXGS_SH_EVAL && count != 1) return fail_msg("mode eval_sh takes exactly one view");
+    if (!views) return fail_msg("NULL argument (views)");
+    if (sh && (sh_dc || sh_rest)) return fail_msg("both sh and the pair (sh_dc, sh_rest) are set");
+    if (!sh && layout != TEXGS_SH_LAYOUT_KC) return fail_msg("the pair (sh_dc, sh_rest) has layout 0 only");
+    if (n == 0) return 0;
+    if (!sh && !sh_dc) return fail_msg("NULL argument (sh, or sh_dc of the pair)");
+    if (!sh && !sh_rest && degree > 0) return fail_msg("NULL argument (sh_rest: read at degree >= 1)");
+    if (((uintptr_t)sh | (uintptr_t)sh_dc | (uintptr_t)sh_rest) & 3) return fail_msg("sh, sh_dc and sh_rest must be 4-byte aligned");
+    return 0;
+}
+
+int texgs_sh_colors_forward(const TexGSShColors* c, const TexGSShColorView* views, int32_t count, void* stream) {
+    if (!c) return fail_msg("sh colours descriptor is NULL");
+    if (int r = check_sh_colors(c->n, c->coeffs, c->degree, c->layout, c->mode, count, c->sh, c->sh_dc, c->sh_rest, views)) return r;
+    if (c->n == 0) return 0;
+    if (c->degree > 0 && !c->xyz) return fail_msg("NULL argument (xyz: read at degree >= 1)");
+    if ((uintptr_t)c->xyz & 3) return fail_msg("xyz must be 4-byte aligned");
+    for (int v = 0; v < count; ++v) {
+        if (!views[v].colors) return fail_msg("NULL argument (a view's colors)");
+        if (c->degree > 0 && c->mode == TEXGS_SH_COLORS && !views[v].campos) return fail_msg("NULL argument (a view's campos: read at degree >= 1)");
+        if (((uintptr_t)views[v].colors | (uintptr_t)views[v].campos) & 3) return fail_msg("a view's campos and colors must be 4-byte aligned");
+    }
+    hipStream_t s = (hipStream_t)stream;
+    return launched("sh_colors_forward", launch_sh_colors(c, views, count, s), s, false);
+}
+
+int texgs_sh_colors_backward(const TexGSShColorsGrad* g, const TexGSShColorGradView* views, int32_t count, void* stream) {
+    if (!g) return fail_msg("sh colours backward descriptor is NULL");
+    if (int r = check_sh_colors(g->n, g->coeffs, g->degree, g->layout, g->mode, count, g->sh, g->sh_dc, g->sh_rest, views)) return r;
+    if (g->accumulate != 0 && g->accumulate != 1) return fail_msg("accumulate must be 0 or 1");
+    if (g->n == 0) return 0;
+    if (!g->d_sh && !g->d_sh_dc && !g->d_sh_rest && !g->d_xyz)
+        return fail_msg("no output requested (d_sh, d_sh_dc, d_sh_rest and d_xyz are all NULL)");
+    if (g->d_sh && !g->sh) return fail_msg("d_sh belongs to sh, which is NULL");
+    if ((g->d_sh_dc || g->d_sh_rest) && g->sh) return fail_msg("d_sh_dc and d_sh_rest belong to the pair, but sh is set");
+    if (g->degree > 0 && !g->xyz) return fail_msg("NULL argument (xyz: read at degree >= 1)");
+    if (((uintptr_t)g->xyz | (uintptr_t)g->d_sh | (uintptr_t)g->d_sh_dc | (uintptr_t)g->d_sh_rest | (uintptr_t)g->d_xyz) & 3)
+        return fail_msg("xyz, d_sh, d_sh_dc, d_sh_rest and d_xyz must be 4-byte aligned");
+    for (int v = 0; v < count; ++v) {
+        if (!views[v].g_colors) return fail_msg("NULL argument (a view's g_colors)");
+        if (g->degree > 0 && g->mode == TEXGS_SH_COLORS && !views[v].campos) return fail_msg("NULL argument (a view's campos: read at degree >= 1)");
+        if (((uintptr_t)views[v].g_colors | (uintptr_t)views[v].campos) & 3) return fail_msg("a view's campos and g_colors must be 4-byte aligned");
+    }
+    hipStream_t s = (hipStream_t)stream;
+    return launched("sh_colors_backward", launch_sh_colors_backward(g, views, count, s), s, false);
+}
+
+}  // extern "C"

@@ -11,6 +11,8 @@
 // A thread takes 4 consecutive pixels, so its selected pixels have consecutive ranks and a workgroup's rows are one contiguous run:
 // the 12-byte xyz rows are staged in LDS and stored as dense dwords.
 #include "common.h"
+#include "abi_support.h"
+#include "texgs_surface.h"
 
 namespace {
 
@@ -233,12 +235,12 @@ inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
 
-size_t surface_temp_bytes(int H, int W) {
+static size_t surface_temp_bytes(int H, int W) {
     const uint32_t n = (uint32_t)H * (uint32_t)W;
     return (SF_INV_BYTES + (size_t)surface_tiles(n) * sizeof(uint32_t) + 255) & ~(size_t)255;
 }
 
-hipError_t launch_surface_points(const TexGSSurfacePoints* p, void* temp, hipStream_t s) {
+static hipError_t launch_surface_points(const TexGSSurfacePoints* p, void* temp, hipStream_t s) {
     const uint32_t n = (uint32_t)p->height * (uint32_t)p->width;
     const uint32_t tiles = surface_tiles(n);
     double* inv = (double*)temp;
@@ -257,7 +259,7 @@ hipError_t launch_surface_points(const TexGSSurfacePoints* p, void* temp, hipStr
     return hipGetLastError();
 }
 
-hipError_t launch_surface_compose(const TexGSSurfaceCompose* c, hipStream_t s) {
+static hipError_t launch_surface_compose(const TexGSSurfaceCompose* c, hipStream_t s) {
     const uint32_t n = (uint32_t)c->height * (uint32_t)c->width;
     const int vec_in = aligned16(c->alpha) && aligned16(c->rank);
     const int vec_out = aligned16(c->out) && (n % 4u == 0u);        // the planes start n floats apart
@@ -265,3 +267,49 @@ hipError_t launch_surface_compose(const TexGSSurfaceCompose* c, hipStream_t s) {
                        (uint32_t)c->rows, n, vec_in, vec_out);
     return hipGetLastError();
 }
+
+extern "C" {
+
+// include/texgs_surface.h: every argument is checked before the first launch, so a refused call has changed nothing
+static int check_surface_image(int32_t H, int32_t W) {
+    if (H <= 0 || W <= 0) return fail_msg("image size must be positive");
+    if (H > TEXGS_SURFACE_MAX_SIDE || W > TEXGS_SURFACE_MAX_SIDE)
+        return failf("%lld x %lld: an image side above 16384 is not supported", (long long)H, (long long)W);
+    if ((long long)H * W >= (1ll << 31)) return fail_msg("image too large: height * width must be below 2^31");
+    return 0;
+}
+
+size_t texgs_surface_temp_bytes(int32_t height, int32_t width) {
+    return check_surface_image(height, width) ? 0 : surface_temp_bytes(height, width);
+}
+
+int texgs_surface_points(const TexGSSurfacePoints* p, void* temp, size_t temp_bytes, void* stream) {
+    if (!p) return fail_msg("surface descriptor is NULL");
+    if (int r = check_surface_image(p->height, p->width)) return r;
+    if (!p->depth || !p->alpha || !p->full_proj || !p->xyz || !p->count || !temp)
+        return fail_msg("NULL argument (depth, alpha, full_proj, xyz, count or temp)");
+    if (!(p->zfar == p->zfar) || !(p->znear == p->znear) || p->zfar == p->znear) return fail_msg("zfar and znear must be two different numbers");
+    if (!(p->threshold == p->threshold)) return fail_msg("threshold is NaN");
+    if ((long long)p->capacity < (long long)p->height * p->width)
+        return fail_msg("capacity must be at least height * width (the count is not known before the launches)");
+    if (((uintptr_t)p->depth | (uintptr_t)p->alpha | (uintptr_t)p->full_proj | (uintptr_t)p->xyz | (uintptr_t)p->alpha_sel | (uintptr_t)p->rank |
+         (uintptr_t)p->count) & 3)
+        return fail_msg("depth, alpha, full_proj, xyz, alpha_sel, rank and count must be 4-byte aligned");
+    if (((uintptr_t)p->index | (uintptr_t)temp) & 7) return fail_msg("index and temp must be 8-byte aligned");
+    if (temp_bytes < surface_temp_bytes(p->height, p->width)) return fail_msg("temp is smaller than texgs_surface_temp_bytes");
+    hipStream_t s = (hipStream_t)stream;
+    return launched("surface_points", launch_surface_points(p, temp, s), s, false);
+}
+
+int texgs_surface_compose(const TexGSSurfaceCompose* c, void* stream) {
+    if (!c) return fail_msg("compose descriptor is NULL");
+    if (int r = check_surface_image(c->height, c->width)) return r;
+    if (c->rows < 0) return fail_msg("rows < 0");
+    if (!c->rank || !c->alpha || !c->out || (c->rows > 0 && !c->values)) return fail_msg("NULL argument (values, rank, alpha or out)");
+    if (((uintptr_t)c->values | (uintptr_t)c->rank | (uintptr_t)c->alpha | (uintptr_t)c->background | (uintptr_t)c->out) & 3)
+        return fail_msg("values, rank, alpha, background and out must be 4-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    return launched("surface_compose", launch_surface_compose(c, s), s, false);
+}
+
+}  // extern "C"

@@ -5,8 +5,11 @@
 //
 // Every result is written by ordinary vector stores / vector atomics from device code; nothing here uses the scalar memory path.
 #include "common.h"
+#include "abi_support.h"
 
 #include <algorithm>
+
+static int hashgrid_levels(const TexGSHashGrid* g, float* scale, uint32_t* res, uint32_t* size, uint32_t* offset, uint32_t* n_params);
 
 namespace {
 
@@ -194,7 +197,7 @@ int cu_count() {
 
 }  // namespace
 
-int hashgrid_levels(const TexGSHashGrid* g, float* scale, uint32_t* res, uint32_t* size, uint32_t* offset, uint32_t* n_params) {
+static int hashgrid_levels(const TexGSHashGrid* g, float* scale, uint32_t* res, uint32_t* size, uint32_t* offset, uint32_t* n_params) {
     if (g->n_levels < 1 || g->n_levels > TEXGS_HASHGRID_MAX_LEVELS) return -1;
     if (g->n_features != TEXGS_HASHGRID_FEATURES) return -2;
     if (g->log2_hashmap_size < 1 || g->log2_hashmap_size > 24) return -3;
@@ -216,9 +219,9 @@ int hashgrid_levels(const TexGSHashGrid* g, float* scale, uint32_t* res, uint32_
     return 0;
 }
 
-hipError_t launch_hashgrid_forward(const TexGSHashGrid* g, const float* params, const float* x, int N, float* enc, hipStream_t s) {
+static hipError_t launch_hashgrid_forward(const TexGSHashGrid* g, const float* params, const float* x, int N, float* enc, hipStream_t s) {
     HGDev d;
-    if (hg_device_table(g, &d)) return hipErrorInvalidValue;      // (abi.hip rejects such a grid first, with the reason)
+    if (hg_device_table(g, &d)) return hipErrorInvalidValue;      // (check_hashgrid below rejects such a grid first, with the reason)
     const uint64_t lanes = (uint64_t)N * d.L;
     if (lanes == 0) return hipSuccess;
     hipLaunchKernelGGL(k_hg_forward, dim3((uint32_t)((lanes + HG_FWD_BLOCK - 1) / HG_FWD_BLOCK)), dim3(HG_FWD_BLOCK), 0, s, d, params, x,
@@ -226,11 +229,11 @@ hipError_t launch_hashgrid_forward(const TexGSHashGrid* g, const float* params, 
     return hipGetLastError();
 }
 
-size_t hashgrid_backward_temp_bytes(const TexGSHashGrid* g, int N) {
+static size_t hashgrid_backward_temp_bytes(const TexGSHashGrid* g, int N) {
     return (size_t)g->n_levels * (size_t)(N > 0 ? N : 0) * 3 * sizeof(float);
 }
 
-hipError_t launch_hashgrid_backward(const TexGSHashGrid* g, const float* params, const float* x, const float* d_enc, int N, float* d_params,
+static hipError_t launch_hashgrid_backward(const TexGSHashGrid* g, const float* params, const float* x, const float* d_enc, int N, float* d_params,
                              float* d_x, void* temp, hipStream_t s) {
     HGDev d;
     if (hg_device_table(g, &d)) return hipErrorInvalidValue;
@@ -266,9 +269,9 @@ hipError_t launch_hashgrid_backward(const TexGSHashGrid* g, const float* params,
     return hipGetLastError();
 }
 
-size_t chamfer_nn_temp_bytes(int P) { return (size_t)(P > 0 ? P : 0) * sizeof(unsigned long long); }
+static size_t chamfer_nn_temp_bytes(int P) { return (size_t)(P > 0 ? P : 0) * sizeof(unsigned long long); }
 
-hipError_t launch_chamfer_nn(const float* a, int P, const float* b, int Q, float* d2, int32_t* idx, void* temp, hipStream_t s) {
+static hipError_t launch_chamfer_nn(const float* a, int P, const float* b, int Q, float* d2, int32_t* idx, void* temp, hipStream_t s) {
     if (P == 0) return hipSuccess;
     unsigned long long* keys = (unsigned long long*)temp;
     if (hipError_t e = hipMemsetAsync(keys, 0xff, (size_t)P * sizeof(unsigned long long), s)) return e;
@@ -277,3 +280,80 @@ hipError_t launch_chamfer_nn(const float* a, int P, const float* b, int Q, float
     hipLaunchKernelGGL(k_nn_unpack, dim3(((uint32_t)P + 255) / 256), dim3(256), 0, s, (const unsigned long long*)keys, (uint32_t)P, d2, idx);
     return hipGetLastError();
 }
+
+extern "C" {
+
+static int check_hashgrid(const TexGSHashGrid* g, uint32_t* n_params) {
+    if (!g) return fail_msg("grid is NULL");
+    float sc[TEXGS_HASHGRID_MAX_LEVELS];
+    uint32_t r[TEXGS_HASHGRID_MAX_LEVELS], sz[TEXGS_HASHGRID_MAX_LEVELS], off[TEXGS_HASHGRID_MAX_LEVELS];
+    switch (hashgrid_levels(g, sc, r, sz, off, n_params)) {
+    case 0: return 0;
+    case -1: return fail_msg("hash grid: n_levels must be in [1, 16]");
+    case -2: return fail_msg("hash grid: n_features must be 4");
+    case -3: return fail_msg("hash grid: log2_hashmap_size must be in [1, 24]");
+    case -4: return fail_msg("hash grid: base_resolution must be >= 1 and per_level_scale in [1, 16]");
+    case -5: return fail_msg("hash grid: a level's resolution is out of range");
+    default: return fail_msg("hash grid: more than 2^31 parameters");
+    }
+}
+
+int texgs_hashgrid_levels(const TexGSHashGrid* grid, float* scale, uint32_t* res, uint32_t* size, uint32_t* offset, uint32_t* n_params) {
+    uint32_t n = 0;
+    if (int r = check_hashgrid(grid, &n)) return r;
+    float sc[TEXGS_HASHGRID_MAX_LEVELS];
+    uint32_t rs[TEXGS_HASHGRID_MAX_LEVELS], sz[TEXGS_HASHGRID_MAX_LEVELS], off[TEXGS_HASHGRID_MAX_LEVELS];
+    hashgrid_levels(grid, sc, rs, sz, off, &n);
+    for (int l = 0; l < grid->n_levels; ++l) {
+        if (scale) scale[l] = sc[l];
+        if (res) res[l] = rs[l];
+        if (size) size[l] = sz[l];
+        if (offset) offset[l] = off[l];
+    }
+    if (n_params) *n_params = n;
+    return 0;
+}
+
+int texgs_hashgrid_forward(const TexGSHashGrid* grid, const float* params, const float* x, int32_t N, float* enc, void* stream) {
+    uint32_t n = 0;
+    if (int r = check_hashgrid(grid, &n)) return r;
+    if (N < 0) return fail_msg("N < 0");
+    if ((int64_t)N * grid->n_levels * TEXGS_HASHGRID_FEATURES > INT32_MAX) return fail_msg("N * L * F >= 2^31");
+    if (N > 0 && (!params || !x || !enc)) return fail_msg("NULL argument");
+    if (N > 0 && (((uintptr_t)params | (uintptr_t)enc) & 15)) return fail_msg("params and enc must be 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    return launched("hashgrid_forward", launch_hashgrid_forward(grid, params, x, N, enc, s), s, false);
+}
+
+size_t texgs_hashgrid_backward_temp_bytes(const TexGSHashGrid* grid, int32_t N) {
+    uint32_t n = 0;
+    if (!grid || check_hashgrid(grid, &n)) return 0;
+    return hashgrid_backward_temp_bytes(grid, N);
+}
+
+int texgs_hashgrid_backward(const TexGSHashGrid* grid, const float* params, const float* x, const float* d_enc, int32_t N,
+                            float* d_params, float* d_x, void* temp, void* stream) {
+    uint32_t n = 0;
+    if (int r = check_hashgrid(grid, &n)) return r;
+    if (N < 0) return fail_msg("N < 0");
+    if ((int64_t)N * grid->n_levels * TEXGS_HASHGRID_FEATURES > INT32_MAX) return fail_msg("N * L * F >= 2^31");
+    if (N > 0 && (!params || !x || !d_enc)) return fail_msg("NULL argument");
+    if (N > 0 && (((uintptr_t)params | (uintptr_t)d_enc | (uintptr_t)d_params) & 15))
+        return fail_msg("params, d_enc and d_params must be 16-byte aligned");
+    if (N > 0 && d_x && !temp) return fail_msg("temp is NULL (d_x needs texgs_hashgrid_backward_temp_bytes)");
+    hipStream_t s = (hipStream_t)stream;
+    return launched("hashgrid_backward", launch_hashgrid_backward(grid, params, x, d_enc, N, d_params, d_x, temp, s), s, false);
+}
+
+size_t texgs_chamfer_nn_temp_bytes(int32_t P) { return chamfer_nn_temp_bytes(P); }
+
+int texgs_chamfer_nn(const float* a, int32_t P, const float* b, int32_t Q, float* d2, int32_t* idx, void* temp, void* stream) {
+    if (P < 0) return fail_msg("P < 0");
+    if (Q < 1) return fail_msg("the reference set is empty (Q < 1)");
+    if ((int64_t)Q > 65535ll * 512) return fail_msg("Q > 65535 * 512");
+    if (P > 0 && (!a || !b || !d2 || !idx || !temp)) return fail_msg("NULL argument");
+    hipStream_t s = (hipStream_t)stream;
+    return launched("chamfer_nn", launch_chamfer_nn(a, P, b, Q, d2, idx, temp, s), s, false);
+}
+
+}  // extern "C"

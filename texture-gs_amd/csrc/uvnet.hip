@@ -33,6 +33,7 @@
 //           they are 3/4 of the work.  MFMA cycles per wave and layer: 64 x 64 (value) + 72 x 32 (tangents) = 6 400 against 16 384.
 //   NF = 0  k_uv_taylor_bf16x3  all split bf16: the masks then come from the split value column (inference only).
 #include "common.h"
+#include "abi_support.h"
 
 namespace {
 
@@ -848,7 +849,7 @@ static UVNetPtrs uv_net_ptrs(const TexGSUVNet* net) {
 // session; every step between two optimizer updates) pack once and reuse `packed`.
 constexpr size_t UV_PACK_BYTES = (size_t)3 * UV_H * UV_H * sizeof(float);
 
-size_t uv_packed_bytes(int precision) {
+static size_t uv_packed_bytes(int precision) {
     return precision == TEXGS_UV_MIXED ? 2 * UV_PACK_BYTES : (precision == TEXGS_UV_FP32 || precision == TEXGS_UV_BF16X3 ? UV_PACK_BYTES : 0);
 }
 
@@ -861,7 +862,7 @@ static UVArgs uv_args(const TexGSUVNet* net, int precision, const void* packed) 
             precision == TEXGS_UV_FP32 ? nullptr : reinterpret_cast<const uint4*>(p + uv_packed_b16_offset(precision))};
 }
 
-hipError_t launch_uv_pack(const TexGSUVNet* net, int precision, void* packed, hipStream_t s) {
+static hipError_t launch_uv_pack(const TexGSUVNet* net, int precision, void* packed, hipStream_t s) {
     char* p = reinterpret_cast<char*>(packed);
     if (precision != TEXGS_UV_BF16X3)
         hipLaunchKernelGGL(k_uv_pack, dim3(3 * 4 * 64 * 64 / 256), dim3(256), 0, s, net->W2, net->W3, net->W4, reinterpret_cast<float*>(p));
@@ -871,7 +872,7 @@ hipError_t launch_uv_pack(const TexGSUVNet* net, int precision, void* packed, hi
     return hipGetLastError();
 }
 
-hipError_t launch_uv_taylor_packed(const TexGSUVNet* net, int precision, const void* packed, const float* xyz, int N, float* uvs, float* grad_uvs,
+static hipError_t launch_uv_taylor_packed(const TexGSUVNet* net, int precision, const void* packed, const float* xyz, int N, float* uvs, float* grad_uvs,
                             hipStream_t s) {
     if (N <= 0) return hipSuccess;
     const UVArgs a = uv_args(net, precision, packed);
@@ -885,11 +886,11 @@ hipError_t launch_uv_taylor_packed(const TexGSUVNet* net, int precision, const v
 // ---- backward: temp = [packed W2..W4][packed W2^T..W4^T][partials of `uv_backward_blocks(N)` workgroups]
 static int uv_backward_blocks(int N) { const int t = (N + BW_P - 1) / BW_P; return t < 256 ? (t < 1 ? 1 : t) : 256; }
 static size_t uv_backward_part_floats() { return (size_t)3 * UV_H * UV_H + 2 * BW_SMALL * UV_H + 4; }
-size_t uv_backward_temp_bytes(int N) {
+static size_t uv_backward_temp_bytes(int N) {
     return 2 * UV_PACK_BYTES + (size_t)uv_backward_blocks(N) * uv_backward_part_floats() * sizeof(float);
 }
 
-hipError_t launch_uv_backward(const TexGSUVNet* net, const float* xyz, const float* g, int N, const TexGSUVNetGrad* out, void* temp, int mixed,
+static hipError_t launch_uv_backward(const TexGSUVNet* net, const float* xyz, const float* g, int N, const TexGSUVNetGrad* out, void* temp, int mixed,
                        hipStream_t s) {
     const int G = uv_backward_blocks(N);
     float* packed = reinterpret_cast<float*>(temp);
@@ -916,3 +917,46 @@ hipError_t launch_uv_backward(const TexGSUVNet* net, const float* xyz, const flo
     hipLaunchKernelGGL(k_uv_backward_reduce, dim3((n_out + 255) / 256), dim3(256), 0, s, partW, partS, partB5, G, o);
     return st.after_launches();
 }
+
+extern "C" {
+
+static int check_uvnet(const TexGSUVNet* net, int32_t precision) {
+    if (precision != TEXGS_UV_FP32 && precision != TEXGS_UV_BF16X3 && precision != TEXGS_UV_MIXED)
+        return fail_msg("precision must be TEXGS_UV_FP32, TEXGS_UV_BF16X3 or TEXGS_UV_MIXED");
+    if (net->hidden != 128) return fail_msg("the UV-map kernels support the shipped UVNet shape only (hidden width 128)");
+    if (!net->W1 || !net->W2 || !net->W3 || !net->W4 || !net->W5 || !net->emb) return fail_msg("weight pointer is NULL");
+    return 0;
+}
+
+size_t texgs_uv_packed_bytes(int32_t precision) { return uv_packed_bytes(precision); }
+
+int texgs_uv_pack(const TexGSUVNet* net, int32_t precision, void* packed, void* stream) {
+    if (!net || !packed) return fail_msg("NULL argument");
+    if (int r = check_uvnet(net, precision)) return r;
+    hipStream_t s = (hipStream_t)stream;
+    return launched("uv_pack", launch_uv_pack(net, precision, packed, s), s, false);
+}
+
+int texgs_uv_taylor_packed(const TexGSUVNet* net, int32_t precision, const void* packed, const float* xyz, int32_t N, float* uvs,
+                           float* grad_uvs, void* stream) {
+    if (!net || !packed) return fail_msg("NULL argument");
+    if (int r = check_uvnet(net, precision)) return r;
+    if (N < 0) return fail_msg("N < 0");
+    if (N > 0 && (!xyz || !uvs || !grad_uvs)) return fail_msg("NULL argument");   /* (an empty tensor's data pointer is NULL) */
+    hipStream_t s = (hipStream_t)stream;
+    return launched("uv_taylor", launch_uv_taylor_packed(net, precision, packed, xyz, N, uvs, grad_uvs, s), s, false);
+}
+
+size_t texgs_uv_backward_temp_bytes(int32_t N) { return uv_backward_temp_bytes(N < 0 ? 0 : N); }
+
+int texgs_uv_backward(const TexGSUVNet* net, int32_t precision, const float* xyz, const float* g_uvs, int32_t N, const TexGSUVNetGrad* out,
+                      void* temp, void* stream) {
+    if (!net || !out || !temp) return fail_msg("NULL argument");
+    if (int r = check_uvnet(net, precision)) return r;
+    if (N < 0) return fail_msg("N < 0");
+    if (N > 0 && (!xyz || !g_uvs)) return fail_msg("NULL argument");
+    hipStream_t s = (hipStream_t)stream;
+    return launched("uv_backward", launch_uv_backward(net, xyz, g_uvs, N, out, temp, precision != TEXGS_UV_FP32, s), s, false);
+}
+
+}  // extern "C"
